@@ -50,6 +50,14 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
 Sharded layout options: --shard-batch, --shard-pipeline, --no-plan-inside.  N > 1 also carries other_configs.config4_sharded:
 each rank's share of BASELINE config #4 in north_star's layout (row-sharded item table, per-batch all-to-all) and that layout's paired Recall@20.
 Every timed region starts from a collected Python heap with the cyclic collector off (settled_heap).
+
+--dump-outputs DIR (one process only): after the timed steps, what the last step handed its caller -- the trained tables P (users x d)
+and Q (items x d, float32) and that step's per-epoch loss and learning rate with the final rate (float64) -- as DIR/<name>.npy, at most
+64 MB in all (larger tables: a fixed, seeded sample of their rows).  Inputs are seeded, and in such a run the epochs of a step follow from
+the arguments alone (--epochs-per-step, else --min-seconds over --steps nominal epochs of NOMINAL_EPOCH_S) instead of a clock
+calibration, so that the same arguments give the same computation on every run and every build.  The Hogwild kernel's update order
+is still a race: two runs of the Yelp2018 shape (--steps 20) agreed in the learning rates exactly, in the loss to 2e-4 and in the
+tables to 8e-3 (relative norms), so a comparison of two builds needs a tolerance of that order.
 """
 from __future__ import annotations
 
@@ -72,6 +80,8 @@ DIM = 64
 LR0, MAX_LR, REG_U, REG_I = 0.01, 1.0, 0.001, 0.001   # config/BPR.conf:9-10
 FLUSH_EVERY = 16
 SEED = 2018
+NOMINAL_EPOCH_S = 0.6e-3        # the Yelp2018-shape epoch: sets the epochs per step of a --dump-outputs run
+DUMP_BUDGET = 64 << 20          # bytes of all --dump-outputs arrays together
 
 
 def bytes_per_triplet(d: int) -> int:
@@ -264,6 +274,23 @@ def hbm_resident_roofline(capi, schedule="user", p_update="atomic"):
                     "avg_launch_ms": ms, "algorithmic_bytes_per_launch": alg, "triplet_updates_per_s": n2 / ms * 1e3}
         del s
     return out[p_update] if isinstance(p_update, str) else out
+
+
+def write_outputs(out_dir: str, P: np.ndarray, Q: np.ndarray, log: np.ndarray, final_lr: float) -> list:
+    """--dump-outputs: the timed path's result as <name>.npy.  Tables that do not fit DUMP_BUDGET are cut to the same seeded sample
+    of their rows on every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"loss": np.ascontiguousarray(log[:, 0], dtype=np.float64), "lr": np.ascontiguousarray(log[:, 1], dtype=np.float64),
+           "final_lr": np.array([final_lr], dtype=np.float64)}
+    room = DUMP_BUDGET - sum(a.nbytes for a in out.values()) - 4096 * 5          # npy headers
+    frac = min(1.0, room / (P.nbytes + Q.nbytes))
+    for name, t in (("P", P), ("Q", Q)):
+        if frac < 1.0:
+            t = t[np.sort(np.random.default_rng(SEED).choice(t.shape[0], int(t.shape[0] * frac), replace=False))]
+        out[name] = np.ascontiguousarray(t, dtype=np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
 
 
 @contextlib.contextmanager
@@ -589,7 +616,14 @@ def main():
     ap.add_argument("--no-plan-inside", action="store_true",
                     help="sharded mode: plan every epoch at its own start, with the host waiting for the stream to run dry (default: the "
                          "next epoch's plan is enqueued in front of the current epoch's last batch, its row counts read back behind an event)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's trained tables, per-epoch loss and learning rate as DIR/<name>.npy "
+                         "(one process only; the epochs per step then follow from the arguments, not from a clock calibration)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs writes one process's tables: run it with --gpus 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_own_ranks(args.gpus)           # does not return
 
@@ -743,6 +777,8 @@ def main():
         t_epoch = (time.perf_counter() - t0) / (cal - 2)
         if args.epochs_per_step:
             inner = args.epochs_per_step
+        elif dump and args.dump_outputs:       # the outputs must not depend on the clock: nominal epochs, not the measured ones
+            inner = min(inner_max, max(1, math.ceil(round(min_seconds / (steps * NOMINAL_EPOCH_S), 6))))
         else:
             inner = min(inner_max, max(1, math.ceil(min_seconds / (steps * t_epoch))))
             if use_dist:
@@ -775,10 +811,15 @@ def main():
         if dump and os.environ.get("QREC_DIST_TEST_DUMP"):     # functional tests: every rank leaves its tables and its driver log behind
             np.savez(os.path.join(os.environ["QREC_DIST_TEST_DUMP"], f"rank{rank}.npz"), Q=tables.Q.numpy(), P=tables.P.numpy(),
                      log=log, lr=drv["lr"], epochs_per_step=inner)
+        dumped = None
+        if dump and args.dump_outputs:        # after the clock: the last step's result, as its caller receives it
+            P, Q = tables.download(np.float32)
+            dumped = write_outputs(args.dump_outputs, P, Q, log, drv["lr"])
         kernel_ms = [ev[k][1].elapsed_ms_since(ev[k][0]) for k in range(first_timed, total)]
         leg = {"n": n, "chunk": CHUNK, "inner": inner, "elapsed": elapsed, "steps": steps, "final_loss": float(log[-1, 0]), "final_lr": drv["lr"],
                "avg_kernel_ms": float(np.mean(kernel_ms)), "n_batches": n_batches, "q_floats": int(tables.Q.nbytes // 4), "moved": None,
-               "fetch_pipelined": False, "plan": None, "ld": tables.ld, "P0": P0, "p_update": sgd.p_update, "collision_density": sgd.collision}
+               "fetch_pipelined": False, "plan": None, "ld": tables.ld, "P0": P0, "p_update": sgd.p_update, "collision_density": sgd.collision,
+               "dumped": dumped}
         if sharded:
             leg["moved"] = float(control.allreduce_host(np.array([dstep.exchange.bytes_moved / max(total, 1)]))[0])
             leg["fetch_pipelined"] = dstep.exchange.pipeline is not None
@@ -910,6 +951,7 @@ def main():
                        **({"xgmi_bytes_per_epoch_all_ranks": moved, "batches_per_epoch": leg["n_batches"],
                            "fetch_pipelined": leg["fetch_pipelined"], "plan": leg["plan"]} if sharded else {})},
             **({"multi_gpu": multi} if multi is not None else {}),
+            **({"dumped_outputs": {"dir": args.dump_outputs, "arrays": leg["dumped"]}} if leg["dumped"] else {}),
             "roofline": {"bound": "hbm", "kernel": kernel,
                          "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,

@@ -1,17 +1,15 @@
 """INTEGRATION.md s2, executed: the stub a QRec maintainer would add (``model/ranking/BPR.py`` binding libqrec_hip.so with
-ctypes) is cut out of INTEGRATION.md, dropped into an overlay of the REAL reference tree (every other file is the
-reference's own, by symlink: base/, data/, util/, QRec.py, the datasets) and run through the reference's own
-``QRec(conf).execute()`` on the FilmTrust conf of the recorded golden run.  It must reproduce that run of the unmodified
-reference: final P and Q, every epoch's loss and learning rate, the measure strings, the state of Python's generator.
+ctypes) is cut out of INTEGRATION.md and installed as the BPR model of a QRec framework -- this repository's restatement of the
+reference's (``qrec_amd``: QRec.py, base/, data/, util/; ``base.iterativeRecommender``, which the stub imports, is its
+IterativeRecommender) -- and run through ``QRec(conf).execute()`` on the FilmTrust conf of the recorded golden run, with the split
+written back to rating files from the fixture.  It must reproduce that run of the unmodified reference: final P and Q, every epoch's
+loss and learning rate, the measure strings, the state of Python's generator.
 
-There is no GPU where the reference tree is (and no reference tree where the GPU is), so the device half of the C ABI is
-answered by tests/integration/shim.c: host entry points forwarded to the real libqrec_hip.so, the SGD / sum-of-squares
-entry points by the oracle's C restatement.  The GPU kernels behind those two symbols are held to the same oracle and the
-same golden run in tests/test_gpu_bpr.py; this test is about the binding."""
+The stub binds the real libqrec_hip.so (QREC_HIP_LIB): its sampler, the order-exact SGD kernel and the sum-of-squares reduction
+run on the device, and so does the framework's ranking evaluation."""
 import json
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -19,23 +17,21 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "base")) or shutil.which("gcc") is None,
-                                reason="needs the reference tree (build container only) and gcc")
 
 RUNNER = r'''
 import io, json, os, random, sys, types
 from contextlib import redirect_stdout
 import numpy as np
-nb = types.ModuleType("numba"); nb.jit = lambda *a, **k: (lambda f: f)
-mkl = types.ModuleType("mkl"); mkl.set_num_threads = lambda n: None; mkl.get_max_threads = lambda: 1
-sys.modules.update(numba=nb, mkl=mkl, tensorflow=types.ModuleType("tensorflow"))
 sys.dont_write_bytecode = True
-sys.path.insert(0, os.getcwd())
-from QRec import QRec
-from util.config import ModelConf
-import model.ranking.BPR as B
+sys.path.insert(0, os.environ["QREC_ROOT"])
+import qrec_amd.base, qrec_amd.base.iterativeRecommender
+sys.modules.update({"base": qrec_amd.base, "base.iterativeRecommender": qrec_amd.base.iterativeRecommender})
+# the stub takes the place of model/ranking/BPR.py: QRec resolves model.name through this module
+B = types.ModuleType("qrec_amd.model.ranking.BPR"); B.__file__ = os.path.abspath("BPR.py")
+exec(compile(open(B.__file__).read(), B.__file__, "exec"), B.__dict__)
+sys.modules[B.__name__] = B
+from qrec_amd.QRec import QRec
+from qrec_amd.util.config import ModelConf
 assert "QREC_HIP_LIB" in open(B.__file__).read()            # it IS the stub
 epochs = []
 orig = B.BPR.isConverged
@@ -70,30 +66,21 @@ def _stub_source():
     return block.group(1)
 
 
-def test_integration_md_stub_runs_inside_the_reference_tree_and_reproduces_the_reference_run(tmp_path):
-    from helpers import load_golden
+@pytest.mark.gpu
+def test_integration_md_stub_runs_inside_the_qrec_framework_and_reproduces_the_reference_run(tmp_path):
+    from helpers import load_golden, rows_from_golden
     meta, z = load_golden("bpr_filmtrust")
-    # the overlay: the reference tree by symlink, model/ranking/BPR.py replaced by the stub
+    # the run's tree: the stub, the runner, the conf and the FilmTrust split it names, in the fixture's row order (ids are assigned by
+    # first appearance, so the loader gives the recorded ids back)
     tree = tmp_path / "tree"
-    (tree / "model" / "ranking").mkdir(parents=True)
-    for name in os.listdir(REF):
-        if name not in ("model", ".git"):
-            os.symlink(os.path.join(REF, name), tree / name)
-    for name in os.listdir(os.path.join(REF, "model")):
-        if name != "ranking":
-            os.symlink(os.path.join(REF, "model", name), tree / "model" / name)
-    for name in os.listdir(os.path.join(REF, "model", "ranking")):
-        if name != "BPR.py":
-            os.symlink(os.path.join(REF, "model", "ranking", name), tree / "model" / "ranking" / name)
-    (tree / "model" / "ranking" / "BPR.py").write_text(_stub_source())
+    (tree / "dataset" / "FilmTrust").mkdir(parents=True)
+    train, test = rows_from_golden(z)
+    for name, rows in (("trainset.txt", train), ("testset.txt", test)):
+        (tree / "dataset" / "FilmTrust" / name).write_text("".join(f"{u} {i} {r}\n" for u, i, r in rows))
+    (tree / "BPR.py").write_text(_stub_source())
     (tree / "run_stub.py").write_text(RUNNER)
     (tree / "bpr.conf").write_text(meta["conf"])
-    shim = tmp_path / "libqrec_shim.so"
-    subprocess.run(["gcc", "-O2", "-shared", "-fPIC", "-o", str(shim), os.path.join(ROOT, "tests", "integration", "shim.c"), "-ldl"], check=True)
-    from oracle import c as O
-    O.lib()                                                       # builds oracle/libqrec_oracle.so if needed
-    env = dict(os.environ, QREC_HIP_LIB=str(shim), QREC_REAL_LIB=os.path.join(ROOT, "qrec_amd", "libqrec_hip.so"),
-               QREC_ORACLE_LIB=os.path.join(ROOT, "oracle", "libqrec_oracle.so"), PYTHONDONTWRITEBYTECODE="1")
+    env = dict(os.environ, QREC_HIP_LIB=os.path.join(ROOT, "qrec_amd", "libqrec_hip.so"), QREC_ROOT=ROOT, PYTHONDONTWRITEBYTECODE="1")
     env.pop("PYTHONPATH", None)
     out = tmp_path / "out.npz"
     run = subprocess.run([sys.executable, "run_stub.py", "bpr.conf", str(meta["seed"]), str(out)], cwd=tree, env=env,
