@@ -35,6 +35,7 @@ extern "C" {
 #define QREC_ERR_HIP (-2)      /* a HIP runtime call failed */
 #define QREC_ERR_NAN (-3)      /* loss is NaN/Inf (base/iterativeRecommender.py:84-86) */
 #define QREC_ERR_UNSUPPORTED (-4)
+#define QREC_ERR_NOT_SPD (-5)  /* a least-squares system is not positive definite (qrec_als_solve_rows) */
 
 #define QREC_F32 0
 #define QREC_F64 1
@@ -725,6 +726,28 @@ int qrec_batch_rows_scatter_add(float *d_block, int32_t ld, int64_t lo, int64_t 
                                 const int32_t *d_j, int32_t B, int64_t n_users, const float *d_src, void *stream);
 int qrec_scatter_add_row_deltas(float *d_table, int32_t ld, const int32_t *d_rows, int64_t n, const float *d_fresh,
                                 const float *d_sent, void *stream);
+
+/* ---- alternating least squares, fp64 (model/ranking/WRMF.py:17-67; als.hip) ------------------------------------------ *
+ * Tables are fp64 [rows][ld], ld in {16, 32, 64, 128} (engine.padded_ld), 1 <= d <= ld, pad columns zero.
+ * qrec_als_gram: d_G[ld][ld] = F^T F over the whole padded rows (the pad block comes out zero).  Fixed partition of the
+ *   rows over the blocks, partials added in block order: bit-reproducible.  Workspace: qrec_als_gram_workspace_bytes.
+ * qrec_als_solve_rows: for every row r of the CSR (d_indptr[n_rows + 1], d_indices into the rows of d_F, d_c per entry)
+ *       A_r = G + sum c f f^T + lambda I   (leading d x d block),   b_r = sum (1 + c) f,   X[r] = A_r^-1 b_r   (Cholesky)
+ *   and, when d_loss is not NULL, *d_loss = sum_r sum_k (1 - X_old[r] . f_k)^2 with the rows of X before this call
+ *   (WRMF.py:37-38).  Rows with more than QREC_ALS_SPLIT_DEGREE entries are accumulated in QREC_ALS_SEGMENT-entry segments
+ *   on blocks of their own and their partials added in segment order; every sum has a fixed order (bit-reproducible).
+ *   X is written only when every row succeeded: a non-positive (or NaN) pivot returns QREC_ERR_NOT_SPD, an index outside
+ *   [0, f_rows) or a decreasing indptr QREC_ERR_INVALID, and X and *d_loss are left as they were.  The call waits for
+ *   its stream (it reads the status back).  Workspace: qrec_als_solve_workspace_bytes over the same indptr, on the host. */
+#define QREC_ALS_MAX_D 128
+#define QREC_ALS_SEGMENT 256
+#define QREC_ALS_SPLIT_DEGREE 512
+int qrec_als_gram_workspace_bytes(int64_t rows, int32_t ld, int64_t *bytes);
+int qrec_als_gram(const double *d_F, int64_t rows, int32_t d, int32_t ld, double *d_G, void *d_ws, int64_t ws_bytes, void *stream);
+int qrec_als_solve_workspace_bytes(const int64_t *h_indptr, int64_t n_rows, int32_t ld, int64_t *bytes);
+int qrec_als_solve_rows(const double *d_F, int64_t f_rows, const double *d_G, double *d_X, int64_t n_rows, int32_t d, int32_t ld,
+                        const int64_t *d_indptr, const int32_t *d_indices, const double *d_c, double lambda, double *d_loss,
+                        void *d_ws, int64_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

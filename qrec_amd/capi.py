@@ -150,10 +150,15 @@ _SIGNATURES = {
     "qrec_batch_rows_gather": [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp],
     "qrec_batch_rows_scatter_add": [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp],
     "qrec_scatter_add_row_deltas": [_vp, _i32, _vp, _i64, _vp, _vp, _vp],
+    "qrec_als_gram_workspace_bytes": [_i64, _i32, _vp],
+    "qrec_als_gram": [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp],
+    "qrec_als_solve_workspace_bytes": [_vp, _i64, _i32, _vp],
+    "qrec_als_solve_rows": [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _f64, _vp, _vp, _i64, _vp],
 }
 _RESTYPES = {"qrec_last_error": C.c_char_p, "qrec_ratings_rows": C.c_int64, "qrec_ratings_count": C.c_int32,
              "qrec_ratings_names_bytes": C.c_int64, "qrec_ratings_free": None}
 ERR_UNSUPPORTED = -4
+ERR_NOT_SPD = -5
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1200,3 +1205,30 @@ def batch_rows_scatter_add(d_block, ld: int, lo: int, hi: int, d_u, d_i, d_j, B:
 
 def scatter_add_row_deltas(d_table, ld: int, d_rows, n: int, d_fresh, d_sent, stream=None):
     _check(load().qrec_scatter_add_row_deltas(_dp(d_table), ld, _dp(d_rows), n, _dp(d_fresh), _dp(d_sent), _sh(stream)))
+
+
+# ---- alternating least squares (als.hip) ----------------------------------------------------------------------------------
+def als_gram_workspace_bytes(rows: int, ld: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_als_gram_workspace_bytes(rows, ld, C.byref(out)))
+    return out.value
+
+
+def als_gram(d_F, rows: int, d: int, ld: int, d_G, d_ws, ws_bytes: int, stream=None):
+    """d_G[ld][ld] = F^T F (fp64, fixed-order sums)"""
+    _check(load().qrec_als_gram(_dp(d_F), rows, d, ld, _dp(d_G), _dp(d_ws), ws_bytes, _sh(stream)))
+
+
+def als_solve_workspace_bytes(indptr: np.ndarray, ld: int) -> int:
+    _req(indptr, np.int64, "indptr")
+    out = C.c_int64(0)
+    _check(load().qrec_als_solve_workspace_bytes(_hp(indptr), indptr.size - 1, ld, C.byref(out)))
+    return out.value
+
+
+def als_solve_rows(d_F, f_rows: int, d_G, d_X, n_rows: int, d: int, ld: int, d_indptr, d_indices, d_c, lam: float, d_loss,
+                   d_ws, ws_bytes: int, stream=None):
+    """X[r] = (G + sum c f f^T + lam I)^-1 sum (1 + c) f for every CSR row; waits for the stream.  QRecError with code
+    ERR_NOT_SPD when a system is not positive definite (X untouched)."""
+    _check(load().qrec_als_solve_rows(_dp(d_F), f_rows, _dp(d_G), _dp(d_X), n_rows, d, ld, _dp(d_indptr), _dp(d_indices), _dp(d_c),
+                                      lam, _dp(d_loss), _dp(d_ws), ws_bytes, _sh(stream)))

@@ -648,3 +648,51 @@ class SvdppSgd:
     def download(self):
         return (self.d_Y.numpy()[:, :self.t.d].astype(np.float64), self.d_Bu.numpy().astype(np.float64),
                 self.d_Bi.numpy().astype(np.float64))
+
+
+class AlsSolver:
+    """Implicit-feedback ALS (model/ranking/WRMF.py:17-67) with both fp64 tables resident: ``X`` (users) and ``Y`` (items) in
+    one ``DeviceTables`` (P = X, Q = Y), the rating CSR by user and by item with confidences ``c = alpha * r``, G and the
+    workspaces.  ``epoch()`` = G = Y^T Y, every user's solve (the loss taken from the rows of X before it), G = X^T X, every
+    item's solve; it returns the loss.  Every sum has a fixed order: two runs from the same tables are bit-identical."""
+
+    def __init__(self, X: np.ndarray, Y: np.ndarray, uid: np.ndarray, iid: np.ndarray, rating: np.ndarray, lam: float,
+                 alpha: float = 10.0):
+        n_users, n_items = X.shape[0], Y.shape[0]
+        self.t = DeviceTables(X, Y, np.float64)
+        self.d, self.ld, self.lam = self.t.d, self.t.ld, float(lam)
+        u = np.asarray(uid, dtype=np.int32); i = np.asarray(iid, dtype=np.int32)
+        c = alpha * np.asarray(rating, dtype=np.float64)
+        self.halves = []
+        for rows, cols, n_rows in ((u, i, n_users), (i, u, n_items)):
+            order = np.argsort(rows, kind="stable")
+            indptr = np.zeros(n_rows + 1, dtype=np.int64)
+            np.cumsum(np.bincount(rows, minlength=n_rows), out=indptr[1:])
+            ws = capi.als_solve_workspace_bytes(indptr, self.ld)
+            self.halves.append(dict(n=n_rows, indptr=indptr, d_indptr=DeviceBuffer.from_numpy(indptr),
+                                    d_indices=DeviceBuffer.from_numpy(np.ascontiguousarray(cols[order], dtype=np.int32)),
+                                    d_c=DeviceBuffer.from_numpy(np.ascontiguousarray(c[order])), ws_bytes=ws))
+        self.ws_bytes = max(h["ws_bytes"] for h in self.halves)
+        self.d_ws = DeviceBuffer((max(self.ws_bytes, 256),), np.uint8)
+        self.gram_ws_bytes = capi.als_gram_workspace_bytes(max(n_users, n_items), self.ld)
+        self.d_gram_ws = DeviceBuffer((self.gram_ws_bytes,), np.uint8)
+        self.d_G = DeviceBuffer((self.ld, self.ld), np.float64)
+        self.d_loss = DeviceBuffer.zeros((1,), np.float64)
+
+    def half(self, side: int, with_loss: bool, stream=None):
+        """side 0: solve the users' rows of X against Y; 1: the items' rows of Y against X"""
+        h = self.halves[side]
+        F, X = (self.t.Q, self.t.P) if side == 0 else (self.t.P, self.t.Q)
+        f_rows = self.halves[1 - side]["n"]
+        capi.als_gram(F, f_rows, self.d, self.ld, self.d_G, self.d_gram_ws, self.gram_ws_bytes, stream)
+        capi.als_solve_rows(F, f_rows, self.d_G, X, h["n"], self.d, self.ld, h["d_indptr"], h["d_indices"], h["d_c"], self.lam,
+                            self.d_loss if with_loss else None, self.d_ws, self.ws_bytes, stream)
+
+    def epoch(self, stream=None) -> float:
+        self.half(0, True, stream)
+        self.half(1, False, stream)
+        return float(self.d_loss.numpy(stream)[0])
+
+    def download(self):
+        """(X, Y) as fp64 host arrays [rows, d]"""
+        return self.t.download(np.float64)
