@@ -749,6 +749,64 @@ int qrec_als_solve_rows(const double *d_F, int64_t f_rows, const double *d_G, do
                         const int64_t *d_indptr, const int32_t *d_indices, const double *d_c, double lambda, double *d_loss,
                         void *d_ws, int64_t ws_bytes, void *stream);
 
+/* ---- memory-based rating models, fp64 (model/rating/{UserKNN,ItemKNN,SlopeOne}.py, util/qmath.py:19-115; knn.hip) ----- *
+ * No FMA contraction; every sum runs in the reference's order; no float atomics: a run is bit-identical to the next.
+ * qrec_knn_sweep: for every query t < n_queries (its row: d_q_keys / d_q_vals[d_q_indptr[t] .. d_q_indptr[t + 1]), in the
+ *   reference's dict order) and every candidate label c < n_cands, the similarity of the query's row (x1) and the candidate's
+ *   row (x2) over their common keys, summed in x1's order:
+ *     PCC        sum (a - m1)(b - m2) / (sqrt(sum (a - m1)^2) sqrt(sum (b - m2)^2)), m1 = d_q_means[t], m2 = d_c_means[c];
+ *                a zero denominator gives 1 when a key overlapped, else 0
+ *     COS        sum ab / (sqrt(sum a^2) sqrt(sum b^2)); a zero denominator gives 0
+ *     EUCLIDEAN  1 / sum (a^2 - b^2); a zero total gives 0
+ *     SLOPEONE   sum (a - b) / count (0 when count = 0), and d_count_out[t][c] = count
+ *   into d_out[t * ld_out + c].  Every square is an input, per entry: d_q_sq / d_c_sq = pow((a - m1), 2) / pow((b - m2), 2)
+ *   for PCC, pow(a, 2) / pow(b, 2) for COS and EUCLIDEAN, as the C library's pow gives them (the reference's ``x ** 2``);
+ *   unused (NULL) for SLOPEONE.  The candidates' rows are given inverted: key -> (label, value) in d_c_labels / d_c_vals
+ *   [d_c_indptr[key] .. d_c_indptr[key + 1]), labels ascending within a key.  One workgroup per (query, QREC_KNN_TILE labels).
+ * qrec_knn_topk: query t's neighbour sequence is, when d_q_label[t] = j >= 0 (the query is the candidate
+ *   with label j; labels 0 .. m - 1 are the queries that are candidates, in query order): the earlier queries s < t with the
+ *   value d_S[s][j] (id d_test_code[s]), then the labels c > j with the value d_S[t][c] (id d_lab2id[c]); when j < 0: every
+ *   label c with d_S[t][c].  Each query's first k entries of the stable sort by value, descending (-0.0 == 0.0), go to
+ *   d_ids / d_vals[t * k ..] and their number to d_counts[t].  k > QREC_KNN_MAX_K returns QREC_ERR_UNSUPPORTED.
+ *   Workspace (the transposed query x query block): qrec_knn_topk_workspace_bytes.
+ * qrec_knn_predict: for every row r, the first d_nb_counts[q] neighbours n of query q = d_row_query[r] in order: mode 0
+ *   (UserKNN) looks up key d_row_other[r] (item) in member row n, mode 1 (ItemKNN) key n in member row d_row_other[r] (user);
+ *   the member rows (d_m_indptr / d_m_keys ascending / d_m_vals) are the users' ratings.  Found: sum += s (r - d_nb_means[n]),
+ *   denom += s.  sum == 0: d_pred = d_row_base[r], status FALLBACK; denom == 0: status ZERO_DIVISION; else
+ *   d_pred = d_row_base[r] + sum / denom, status COMPUTED.
+ * qrec_slopeone_batch: the SLOPEONE sweep of queries [q0, q0 + nq) (test items; candidates: all items) into the workspace
+ *   (qrec_slopeone_workspace_bytes(nq, n_items)), then every row r whose query lies in the batch: user u = d_row_user[r] >= 0
+ *   walks its row in dict order (d_u_indptr / d_u_items / d_u_vals): sum += (r + dev) * freq, freqSum += freq;
+ *   d_pred = sum / freqSum (COMPUTED), or d_row_base[r] when freqSum == 0 or u < 0 (FALLBACK).  d_u_*_sorted are the same
+ *   rows with the items ascending (the sweep's inverted index). */
+#define QREC_KNN_PCC 0
+#define QREC_KNN_COS 1
+#define QREC_KNN_EUCLIDEAN 2
+#define QREC_KNN_SLOPEONE 3
+#define QREC_KNN_TILE 2048
+#define QREC_KNN_MAX_K 256
+#define QREC_KNN_COMPUTED 0
+#define QREC_KNN_FALLBACK 1
+#define QREC_KNN_ZERO_DIVISION 2
+int qrec_knn_sweep(int32_t measure, int64_t n_queries, const int64_t *d_q_indptr, const int32_t *d_q_keys, const double *d_q_vals,
+                   const double *d_q_means, const double *d_q_sq, int64_t n_keys, const int64_t *d_c_indptr, const int32_t *d_c_labels,
+                   const double *d_c_vals, const double *d_c_sq, int64_t n_cands, const double *d_c_means, double *d_out, int64_t ld_out, int32_t *d_count_out, int64_t ld_count,
+                   void *stream);
+int qrec_knn_topk_workspace_bytes(int64_t n_queries, int64_t m, int64_t *bytes);
+int qrec_knn_topk(int64_t n_queries, const double *d_S, int64_t ld_S, int64_t m, const int32_t *d_q_label, const int32_t *d_test_code,
+                  const int32_t *d_lab2id, int64_t n_cands, int32_t k, int32_t *d_ids, double *d_vals, int32_t *d_counts, void *d_ws,
+                  int64_t ws_bytes, void *stream);
+int qrec_knn_predict(int32_t mode, int64_t n_rows, const int32_t *d_row_query, const int32_t *d_row_other, const double *d_row_base,
+                     const int32_t *d_nb_ids, const double *d_nb_vals, const int32_t *d_nb_counts, int64_t n_queries, int32_t k,
+                     int64_t n_members, const int64_t *d_m_indptr, const int32_t *d_m_keys, const double *d_m_vals, int64_t n_nb,
+                     const double *d_nb_means, double *d_pred, int32_t *d_status, void *stream);
+int qrec_slopeone_workspace_bytes(int64_t batch, int64_t n_items, int64_t *bytes);
+int qrec_slopeone_batch(int64_t q0, int64_t nq, const int64_t *d_q_indptr, const int32_t *d_q_keys, const double *d_q_vals,
+                        int64_t n_users, const int64_t *d_u_indptr_sorted, const int32_t *d_u_items_sorted, const double *d_u_vals_sorted,
+                        int64_t n_items, int64_t n_rows, const int32_t *d_row_query, const int32_t *d_row_user, const double *d_row_base,
+                        const int64_t *d_u_indptr, const int32_t *d_u_items, const double *d_u_vals, double *d_pred, int32_t *d_status,
+                        void *d_ws, int64_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

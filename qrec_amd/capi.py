@@ -154,11 +154,21 @@ _SIGNATURES = {
     "qrec_als_gram": [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp],
     "qrec_als_solve_workspace_bytes": [_vp, _i64, _i32, _vp],
     "qrec_als_solve_rows": [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _f64, _vp, _vp, _i64, _vp],
+    "qrec_knn_sweep": [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp],
+    "qrec_knn_topk_workspace_bytes": [_i64, _i64, _vp],
+    "qrec_knn_topk": [_i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
+    "qrec_knn_predict": [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "qrec_slopeone_workspace_bytes": [_i64, _i64, _vp],
+    "qrec_slopeone_batch": [_i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                            _i64, _vp],
 }
 _RESTYPES = {"qrec_last_error": C.c_char_p, "qrec_ratings_rows": C.c_int64, "qrec_ratings_count": C.c_int32,
              "qrec_ratings_names_bytes": C.c_int64, "qrec_ratings_free": None}
 ERR_UNSUPPORTED = -4
 ERR_NOT_SPD = -5
+KNN_PCC, KNN_COS, KNN_EUCLIDEAN, KNN_SLOPEONE = 0, 1, 2, 3
+KNN_TILE, KNN_MAX_K = 2048, 256
+KNN_COMPUTED, KNN_FALLBACK, KNN_ZERO_DIVISION = 0, 1, 2
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1232,3 +1242,46 @@ def als_solve_rows(d_F, f_rows: int, d_G, d_X, n_rows: int, d: int, ld: int, d_i
     ERR_NOT_SPD when a system is not positive definite (X untouched)."""
     _check(load().qrec_als_solve_rows(_dp(d_F), f_rows, _dp(d_G), _dp(d_X), n_rows, d, ld, _dp(d_indptr), _dp(d_indices), _dp(d_c),
                                       lam, _dp(d_loss), _dp(d_ws), ws_bytes, _sh(stream)))
+
+
+# ---- memory-based rating models (knn.hip) -----------------------------------------------------------------------------------
+def knn_sweep(measure: int, n_queries: int, d_q_indptr, d_q_keys, d_q_vals, d_q_means, d_q_sq, n_keys: int, d_c_indptr, d_c_labels,
+              d_c_vals, d_c_sq, n_cands: int, d_c_means, d_out, ld_out: int, d_count_out=None, ld_count: int = 0, stream=None):
+    """d_out[t][c] = similarity of query row t (x1) and candidate c (x2), summed in x1's order (include/qrec_hip.h)"""
+    _check(load().qrec_knn_sweep(measure, n_queries, _dp(d_q_indptr), _dp(d_q_keys), _dp(d_q_vals), _dp(d_q_means), _dp(d_q_sq), n_keys,
+                                 _dp(d_c_indptr), _dp(d_c_labels), _dp(d_c_vals), _dp(d_c_sq), n_cands, _dp(d_c_means), _dp(d_out), ld_out,
+                                 _dp(d_count_out), ld_count, _sh(stream)))
+
+
+def knn_topk_workspace_bytes(n_queries: int, m: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_knn_topk_workspace_bytes(n_queries, m, C.byref(out)))
+    return out.value
+
+
+def knn_topk(n_queries: int, d_S, ld_S: int, m: int, d_q_label, d_test_code, d_lab2id, n_cands: int, k: int, d_ids, d_vals, d_counts,
+             d_ws, ws_bytes: int, stream=None):
+    """each query's first k neighbours (stable, value descending); QRecError ERR_UNSUPPORTED when k > KNN_MAX_K"""
+    _check(load().qrec_knn_topk(n_queries, _dp(d_S), ld_S, m, _dp(d_q_label), _dp(d_test_code), _dp(d_lab2id), n_cands, k, _dp(d_ids),
+                                _dp(d_vals), _dp(d_counts), _dp(d_ws), ws_bytes, _sh(stream)))
+
+
+def knn_predict(mode: int, n_rows: int, d_row_query, d_row_other, d_row_base, d_nb_ids, d_nb_vals, d_nb_counts, n_queries: int, k: int,
+                n_members: int, d_m_indptr, d_m_keys, d_m_vals, n_nb: int, d_nb_means, d_pred, d_status, stream=None):
+    _check(load().qrec_knn_predict(mode, n_rows, _dp(d_row_query), _dp(d_row_other), _dp(d_row_base), _dp(d_nb_ids), _dp(d_nb_vals),
+                                   _dp(d_nb_counts), n_queries, k, n_members, _dp(d_m_indptr), _dp(d_m_keys), _dp(d_m_vals), n_nb,
+                                   _dp(d_nb_means), _dp(d_pred), _dp(d_status), _sh(stream)))
+
+
+def slopeone_workspace_bytes(batch: int, n_items: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_slopeone_workspace_bytes(batch, n_items, C.byref(out)))
+    return out.value
+
+
+def slopeone_batch(q0: int, nq: int, d_q_indptr, d_q_keys, d_q_vals, n_users: int, d_us_indptr, d_us_items, d_us_vals, n_items: int,
+                   n_rows: int, d_row_query, d_row_user, d_row_base, d_u_indptr, d_u_items, d_u_vals, d_pred, d_status, d_ws,
+                   ws_bytes: int, stream=None):
+    _check(load().qrec_slopeone_batch(q0, nq, _dp(d_q_indptr), _dp(d_q_keys), _dp(d_q_vals), n_users, _dp(d_us_indptr), _dp(d_us_items),
+                                      _dp(d_us_vals), n_items, n_rows, _dp(d_row_query), _dp(d_row_user), _dp(d_row_base), _dp(d_u_indptr),
+                                      _dp(d_u_items), _dp(d_u_vals), _dp(d_pred), _dp(d_status), _dp(d_ws), ws_bytes, _sh(stream)))

@@ -314,3 +314,23 @@ class Rating:
         if "rated" not in self._csr_cache:
             self._csr_cache["rated"] = self._dict_csr(None)
         return self._csr_cache["rated"]
+
+    def item_rated_csr(self) -> CSR:
+        """All train users per item (rows = item ids, columns = user ids) in ``trainSet_i`` dict order: a duplicated
+        (user, item) pair keeps its last rating at its first position."""
+        if "item_rated" not in self._csr_cache:
+            if self._dedup is not None:
+                du, di, dr = self._dedup
+                self._csr_cache["item_rated"] = user_item_csr(di, du, dr, len(self.item), len(self.user), None, assume_unique=True)
+            else:
+                ni = len(self.item)
+                counts = np.zeros(ni + 1, dtype=np.int64)
+                cols, vals = [], []
+                for i, iid in self.item.items():
+                    col = self.trainSet_i[i]
+                    counts[iid + 1] = len(col)
+                    cols.extend(self.user[u] for u in col)
+                    vals.extend(col.values())
+                self._csr_cache["item_rated"] = CSR(np.cumsum(counts), np.asarray(cols, dtype=np.int32),
+                                                    np.asarray(vals, dtype=np.float64))
+        return self._csr_cache["item_rated"]

@@ -696,3 +696,174 @@ class AlsSolver:
     def download(self):
         """(X, Y) as fp64 host arrays [rows, d]"""
         return self.t.download(np.float64)
+
+
+def _take_rows(csr: CSR, rows: np.ndarray):
+    """(indptr, indices, values) of the CSR's rows ``rows`` (-1: an empty row), in that order"""
+    rows = np.asarray(rows, dtype=np.int64)
+    lens = np.where(rows >= 0, np.diff(csr.indptr)[np.maximum(rows, 0)] if csr.n_rows else 0, 0).astype(np.int64)
+    indptr = np.zeros(rows.size + 1, dtype=np.int64)
+    np.cumsum(lens, out=indptr[1:])
+    starts = np.where(rows >= 0, csr.indptr[np.maximum(rows, 0)] if csr.n_rows else 0, 0)
+    src = np.repeat(starts - indptr[:-1], lens) + np.arange(indptr[-1], dtype=np.int64)
+    return indptr, np.ascontiguousarray(csr.indices[src], dtype=np.int32), np.ascontiguousarray(csr.values[src], dtype=np.float64)
+
+
+def _inverted(csr: CSR, n_keys: int, label_of: np.ndarray):
+    """key -> (label of the row, value), labels ascending within a key: the sweep's candidate side"""
+    lab = label_of[csr.row_ids()].astype(np.int32)
+    order = np.lexsort((lab, csr.indices))
+    indptr = np.zeros(n_keys + 1, dtype=np.int64)
+    np.cumsum(np.bincount(csr.indices, minlength=n_keys), out=indptr[1:])
+    return indptr, np.ascontiguousarray(lab[order]), np.ascontiguousarray(csr.values[order], dtype=np.float64)
+
+
+def libm_squares(x: np.ndarray) -> np.ndarray:
+    """``v ** 2`` of every element as Python computes it: the C library's pow(v, 2.0), which is not always the correctly
+    rounded v * v that the device (or numpy's square) would give -- the reference's similarities square this way
+    (util/qmath.py:25-27,57-60), so the kernels take these squares as inputs"""
+    return np.fromiter((v ** 2 for v in np.asarray(x, dtype=np.float64).tolist()), dtype=np.float64, count=np.size(x))
+
+
+def _dev(a, dtype):
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return DeviceBuffer.from_numpy(a) if a.size else DeviceBuffer((1,), dtype)
+
+
+class CoRatingKnn:
+    """Neighbourhood of UserKNN / ItemKNN (model/rating/{UserKNN,ItemKNN}.py, util/qmath.py:19-115) on the device.
+
+    ``rows`` is the candidates' CSR in the reference's dict order (users -> items for UserKNN, items -> users for ItemKNN),
+    ``means`` their means, ``query_ids`` the candidate id of every query (test user / test item, in testSet order) or -1.
+    The queries that are candidates get the labels 0 .. m - 1 in query order, the other candidates m .. in id order, so that
+    the query x query block of the similarity rows is contiguous.  ``run()`` sweeps every query row (``S[t][label]``, all rows
+    resident) and takes each query's first ``k`` neighbours by the reference's candidate sequence (DESIGN.md s5.7);
+    ``predict()`` walks them for a batch of test rows."""
+
+    def __init__(self, measure: int, rows: CSR, n_keys: int, means: np.ndarray, query_ids: np.ndarray, k: int):
+        if k > capi.KNN_MAX_K:
+            raise ValueError(f"num.neighbors = {k} is above the supported maximum of {capi.KNN_MAX_K}")
+        if k < 1:
+            raise ValueError(f"num.neighbors = {k} must be at least 1")
+        self.measure, self.k = int(measure), int(k)
+        self.n_cands, self.n_keys = rows.n_rows, int(n_keys)
+        q = np.asarray(query_ids, dtype=np.int64)
+        self.n_queries = int(q.size)
+        in_q = q[q >= 0]
+        self.m = int(in_q.size)
+        rest = np.setdiff1d(np.arange(self.n_cands, dtype=np.int64), in_q, assume_unique=True)
+        self.lab2id = np.concatenate([in_q, rest]).astype(np.int32)
+        self.id2lab = np.empty(self.n_cands, dtype=np.int32)
+        self.id2lab[self.lab2id] = np.arange(self.n_cands, dtype=np.int32)
+        self.q_label = np.where(q >= 0, self.id2lab[np.maximum(q, 0)] if self.n_cands else -1, -1).astype(np.int32)
+        self.test_code = np.where(q >= 0, q, -1 - np.arange(q.size)).astype(np.int32)
+        means = np.asarray(means, dtype=np.float64)
+        q_indptr, q_keys, q_vals = _take_rows(rows, q)
+        c_indptr, c_labels, c_vals = _inverted(rows, self.n_keys, self.id2lab)
+        s_bytes = self.n_queries * self.n_cands * 8
+        self.ws_bytes = capi.knn_topk_workspace_bytes(self.n_queries, self.m)
+        hbm = capi.device_info()["hbm_bytes"]
+        need = s_bytes + self.ws_bytes + 3 * (rows.nnz * 12 + self.n_cands * 16)
+        if need > 0.9 * hbm:
+            raise MemoryError(f"the similarity rows of {self.n_queries} queries x {self.n_cands} candidates and the transposed query "
+                              f"block need {need / 2**30:.1f} GiB; the device has {hbm / 2**30:.1f} GiB")
+        q_means = np.where(q >= 0, means[np.maximum(q, 0)] if means.size else 0.0, 0.0)
+        c_means = means[self.lab2id]
+        if self.measure == capi.KNN_PCC:
+            q_sq = libm_squares(q_vals - np.repeat(q_means, np.diff(q_indptr)))
+            c_sq = libm_squares(c_vals - c_means[c_labels])
+        else:
+            q_sq, c_sq = libm_squares(q_vals), libm_squares(c_vals)
+        self.d_q = [_dev(q_indptr, np.int64), _dev(q_keys, np.int32), _dev(q_vals, np.float64), _dev(q_means, np.float64),
+                    _dev(q_sq, np.float64)]
+        self.d_c = [_dev(c_indptr, np.int64), _dev(c_labels, np.int32), _dev(c_vals, np.float64), _dev(c_sq, np.float64),
+                    _dev(c_means, np.float64)]
+        self.d_S = DeviceBuffer((max(self.n_queries, 1), max(self.n_cands, 1)), np.float64)
+        self.d_ws = DeviceBuffer((self.ws_bytes,), np.uint8)
+        self.d_q_label, self.d_test_code, self.d_lab2id = _dev(self.q_label, np.int32), _dev(self.test_code, np.int32), _dev(self.lab2id, np.int32)
+        self.d_ids = DeviceBuffer((max(self.n_queries, 1), self.k), np.int32)
+        self.d_vals = DeviceBuffer((max(self.n_queries, 1), self.k), np.float64)
+        self.d_counts = DeviceBuffer.zeros((max(self.n_queries, 1),), np.int32)
+
+    def sweep(self, stream=None):
+        capi.knn_sweep(self.measure, self.n_queries, *self.d_q, self.n_keys, *self.d_c[:4], self.n_cands, self.d_c[4], self.d_S,
+                       max(self.n_cands, 1), None, 0, stream)
+
+    def topk(self, stream=None):
+        if self.n_cands:
+            capi.knn_topk(self.n_queries, self.d_S, self.n_cands, self.m, self.d_q_label, self.d_test_code, self.d_lab2id, self.n_cands,
+                          self.k, self.d_ids, self.d_vals, self.d_counts, self.d_ws, self.ws_bytes, stream)
+
+    def run(self, stream=None):
+        self.sweep(stream)
+        self.topk(stream)
+
+    def similarities(self, queries=None) -> np.ndarray:
+        """S[t][candidate id] = similarity(row of query t, row of the candidate), query t's row being x1 -- for the given query
+        indices (default: all), as fp64 [len, n_cands]"""
+        queries = np.arange(self.n_queries) if queries is None else np.asarray(queries, dtype=np.int64)
+        out = np.empty((queries.size, self.n_cands), dtype=np.float64)
+        for a, t in enumerate(queries.tolist()):
+            out[a] = self.d_S.read_rows(int(t), 1)[0][self.id2lab]
+        return out
+
+    def neighbours(self):
+        """(ids [n_queries, k] -- candidate id, or -1 - s for the query s that is no candidate --, similarities, counts)"""
+        n = self.n_queries
+        counts = self.d_counts.numpy()[:n]
+        return self.d_ids.numpy()[:n], self.d_vals.numpy()[:n], counts
+
+    def predict(self, mode: int, row_query, row_other, row_base, members: CSR, nb_means, stream=None):
+        """(pred, status) of test rows: mode 0 (UserKNN) looks up item row_other in each neighbour's row of ``members`` (users'
+        ratings, items ascending), mode 1 (ItemKNN) each neighbour item in user row_other's row"""
+        n = int(np.asarray(row_query).size)
+        if n == 0:
+            return np.zeros(0), np.zeros(0, np.int32)
+        d_pred, d_status = DeviceBuffer((n,), np.float64), DeviceBuffer((n,), np.int32)
+        nb_means = np.asarray(nb_means, dtype=np.float64)
+        capi.knn_predict(mode, n, _dev(row_query, np.int32), _dev(row_other, np.int32), _dev(row_base, np.float64), self.d_ids,
+                         self.d_vals, self.d_counts, self.n_queries, self.k, members.n_rows, _dev(members.indptr, np.int64),
+                         _dev(members.indices, np.int32), _dev(members.values, np.float64), nb_means.size, _dev(nb_means, np.float64),
+                         d_pred, d_status, stream)
+        return d_pred.numpy(stream), d_status.numpy(stream)
+
+
+class SlopeOneSolver:
+    """SlopeOne (model/rating/SlopeOne.py) on the device: test items in batches; per batch the deviation rows
+    ``diffAverage[i][j]`` / ``freq[i][j]`` of every training item j are swept into a scratch buffer and the test rows of the
+    batch's items predicted from it.  The full table is never kept."""
+
+    def __init__(self, item_rows: CSR, user_rows: CSR, query_items: np.ndarray, batch: int | None = None):
+        self.n_items, self.n_users = item_rows.n_rows, user_rows.n_rows
+        q = np.asarray(query_items, dtype=np.int64)
+        self.n_queries = int(q.size)
+        if batch is None:           # about 1 GiB of scratch
+            batch = max(1, min(self.n_queries, (1 << 30) // max(12 * self.n_items, 1)))
+        self.batch = int(batch)
+        self.d_q = [_dev(a, t) for a, t in zip(_take_rows(item_rows, q), (np.int64, np.int32, np.float64))]
+        srt = user_rows.sorted_rows()
+        self.d_us = [_dev(srt.indptr, np.int64), _dev(srt.indices, np.int32), _dev(srt.values, np.float64)]
+        self.d_u = [_dev(user_rows.indptr, np.int64), _dev(user_rows.indices, np.int32), _dev(user_rows.values, np.float64)]
+        self.ws_bytes = capi.slopeone_workspace_bytes(self.batch, self.n_items)
+        self.d_ws = DeviceBuffer((self.ws_bytes,), np.uint8)
+
+    def predict(self, row_query, row_user, row_base, stream=None):
+        n = int(np.asarray(row_query).size)
+        d_pred, d_status = DeviceBuffer((max(n, 1),), np.float64), DeviceBuffer((max(n, 1),), np.int32)
+        d_rq, d_ru, d_rb = _dev(row_query, np.int32), _dev(row_user, np.int32), _dev(row_base, np.float64)
+        for q0 in range(0, self.n_queries, self.batch):
+            nq = min(self.batch, self.n_queries - q0)
+            capi.slopeone_batch(q0, nq, *self.d_q, self.n_users, *self.d_us, self.n_items, n, d_rq, d_ru, d_rb, *self.d_u, d_pred,
+                                d_status, self.d_ws, self.ws_bytes, stream)
+        return d_pred.numpy(stream)[:n], d_status.numpy(stream)[:n]
+
+    def deviations(self, q0: int, nq: int, stream=None):
+        """(diffAverage [nq, n_items], freq [nq, n_items]) of queries [q0, q0 + nq): one batch swept, nothing predicted"""
+        ws = capi.slopeone_workspace_bytes(nq, self.n_items)
+        d_ws = DeviceBuffer((ws,), np.uint8)
+        capi.slopeone_batch(q0, nq, *self.d_q, self.n_users, *self.d_us, self.n_items, 0, None, None, None, *self.d_u, None, None,
+                            d_ws, ws, stream)
+        raw = d_ws.numpy(stream)
+        dev = raw[:nq * self.n_items * 8].view(np.float64).reshape(nq, self.n_items)
+        freq = raw[nq * self.n_items * 8: nq * self.n_items * 12].view(np.int32).reshape(nq, self.n_items)
+        return dev.copy(), freq.copy()
