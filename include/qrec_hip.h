@@ -255,7 +255,8 @@ int qrec_epoch_sum_table(const void *d_X, int64_t rows, int dtype, int32_t ld, d
 /* Rating-prediction MF family, order-exact: variant 0 = model/rating/BasicMF.py:9-26 (config #1),
  * 1 = model/rating/PMF.py:9-28 (regU, regI), 2 = model/rating/SVD.py:13-35 (biases d_Bu/d_Bi of the
  * tables' dtype, regB, global mean), 3 = model/rating/EE.py:15-34 (Euclidean embedding; *d_loss then also
- * carries the per-rating regU*|P[u]-Q[i]|^2 term of EE.py:25).  Rows are visited in array order (the caller passes the current
+ * carries the per-rating regU*|P[u]-Q[i]|^2 term of EE.py:25), 4 = model/rating/SocialMF.py:14-24 (PMF's arithmetic on
+ * copies of P[u], Q[i]: the Q[i] update sees the old P[u]).  Rows are visited in array order (the caller passes the current
  * trainingData order); *d_loss receives sum(error^2).                                          */
 int qrec_mf_sgd_ordered(void *d_P, void *d_Q, int dtype, int32_t d, int32_t ld,
                         const int32_t *d_u, const int32_t *d_i, const double *d_rating, int64_t n,
@@ -806,6 +807,39 @@ int qrec_slopeone_batch(int64_t q0, int64_t nq, const int64_t *d_q_indptr, const
                         int64_t n_items, int64_t n_rows, const int32_t *d_row_query, const int32_t *d_row_user, const double *d_row_base,
                         const int64_t *d_u_indptr, const int32_t *d_u_items, const double *d_u_vals, double *d_pred, int32_t *d_status,
                         void *d_ws, int64_t ws_bytes, void *stream);
+
+
+/* ---- social-trust rating models (model/rating/{SoRec,SoReg,SocialMF,RSTE,SREE}.py), fp64 tables, order-exact ----------
+ * qrec_rste_sgd_ordered: RSTE.py:22-40 strictly in array order (one wavefront).  d_fe_indptr [n_users+1] / d_fe_ids / d_fe_w:
+ *   every user's followees in dict order with their weights; d_fe_den [n_users]: their weight sum as the host's numpy gives
+ *   it.  den != 0: pred = alpha*P[u].Q[i] + ((1-alpha)*sum_f w_f P[f].Q[i])/den, else P[u].Q[i]; *d_loss = sum(error^2).
+ * qrec_social_user_pass: the per-user social pass, mode QREC_SOCIAL_SOCIALMF (SocialMF.py:25-41, coef = regS),
+ *   QREC_SOCIAL_SOREG (SoReg.py:58-74, coef = alpha) or QREC_SOCIAL_SREE (SREE.py:50-63, coef = alpha).  Step k is user
+ *   d_step_user[k]; its followees are d_fe_ids[d_fe_indptr[k] ..] with weights d_fe_w (SoReg: Sim per edge), its followers
+ *   (SoReg only) d_fr_*.  Loss terms go to d_slots: one per step for SocialMF, one per followee edge for SoReg and SREE.
+ * qrec_sorec_relation_pass: SoRec.py:41-58 over relations k = (d_rel_u, d_rel_v, d_rel_t) with the weight d_rel_w;
+ *   d_slots[k] = regS*euv^2.
+ * Both social passes run the level schedule d_order / d_level_ptr [n_levels+1] (steps of level L: d_order[d_level_ptr[L] ..
+ *   d_level_ptr[L+1]), no two of them conflicting on a row) in one workgroup of n_waves (1..QREC_SOCIAL_MAX_WAVES)
+ *   wavefronts; any valid schedule gives the bits of the sequential walk.
+ * qrec_loss_fold: *d_running = ((*d_running + d_slots[0]) + d_slots[1]) + ... in slot order.                          */
+#define QREC_SOCIAL_SOCIALMF 0
+#define QREC_SOCIAL_SOREG 1
+#define QREC_SOCIAL_SREE 2
+#define QREC_SOCIAL_MAX_WAVES 16
+int qrec_rste_sgd_ordered(double *d_P, double *d_Q, int32_t d, int32_t ld, const int64_t *d_fe_indptr, const int32_t *d_fe_ids,
+                          const double *d_fe_w, const double *d_fe_den, const int32_t *d_u, const int32_t *d_i,
+                          const double *d_rating, int64_t n, double lr, double alpha, double regU, double regI, double *d_loss,
+                          void *stream);
+int qrec_social_user_pass(int mode, double *d_P, int32_t d, int32_t ld, const int32_t *d_step_user, int64_t n_steps,
+                          const int64_t *d_fe_indptr, const int32_t *d_fe_ids, const double *d_fe_w, const int64_t *d_fr_indptr,
+                          const int32_t *d_fr_ids, const double *d_fr_w, const int32_t *d_order, const int32_t *d_level_ptr,
+                          int32_t n_levels, int32_t n_waves, double lr, double coef, double *d_slots, void *stream);
+int qrec_sorec_relation_pass(double *d_P, double *d_Z, int32_t d, int32_t ld, const int32_t *d_rel_u, const int32_t *d_rel_v,
+                             const double *d_rel_t, const double *d_rel_w, int64_t n_rel, const int32_t *d_order,
+                             const int32_t *d_level_ptr, int32_t n_levels, int32_t n_waves, double lr, double regS, double regZ,
+                             double *d_slots, void *stream);
+int qrec_loss_fold(double *d_running, const double *d_slots, int64_t n, void *stream);
 
 #ifdef __cplusplus
 }

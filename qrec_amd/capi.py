@@ -161,6 +161,11 @@ _SIGNATURES = {
     "qrec_slopeone_workspace_bytes": [_i64, _i64, _vp],
     "qrec_slopeone_batch": [_i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _i64, _vp],
+    "qrec_rste_sgd_ordered": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _vp, _vp],
+    "qrec_social_user_pass": [C.c_int, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _vp,
+                              _vp],
+    "qrec_sorec_relation_pass": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _f64, _f64, _f64, _vp, _vp],
+    "qrec_loss_fold": [_vp, _vp, _i64, _vp],
 }
 _RESTYPES = {"qrec_last_error": C.c_char_p, "qrec_ratings_rows": C.c_int64, "qrec_ratings_count": C.c_int32,
              "qrec_ratings_names_bytes": C.c_int64, "qrec_ratings_free": None}
@@ -660,7 +665,7 @@ def bpr_sgd_hogwild(d_P, d_Q, d: int, ld: int, d_u, d_i, d_j, n: int, chunk: int
                                        _dp(d_driver_state), _sh(stream)))
 
 
-MF_BASIC, MF_PMF, MF_SVD, MF_EE = 0, 1, 2, 3
+MF_BASIC, MF_PMF, MF_SVD, MF_EE, MF_SOCIALMF = 0, 1, 2, 3, 4
 
 
 def mf_sgd_ordered(d_P, d_Q, dtype: int, d: int, ld: int, d_u, d_i, d_rating, n: int, lr: float,
@@ -1285,3 +1290,35 @@ def slopeone_batch(q0: int, nq: int, d_q_indptr, d_q_keys, d_q_vals, n_users: in
     _check(load().qrec_slopeone_batch(q0, nq, _dp(d_q_indptr), _dp(d_q_keys), _dp(d_q_vals), n_users, _dp(d_us_indptr), _dp(d_us_items),
                                       _dp(d_us_vals), n_items, n_rows, _dp(d_row_query), _dp(d_row_user), _dp(d_row_base), _dp(d_u_indptr),
                                       _dp(d_u_items), _dp(d_u_vals), _dp(d_pred), _dp(d_status), _dp(d_ws), ws_bytes, _sh(stream)))
+
+
+# ---- social-trust rating models (social.hip) ---------------------------------------------------------------------------------
+SOCIAL_SOCIALMF, SOCIAL_SOREG, SOCIAL_SREE = 0, 1, 2
+SOCIAL_MAX_WAVES = 16
+
+
+def rste_sgd_ordered(d_P, d_Q, d: int, ld: int, d_fe_indptr, d_fe_ids, d_fe_w, d_fe_den, d_u, d_i, d_rating, n: int, lr: float,
+                     alpha: float, regU: float, regI: float, d_loss, stream=None):
+    """RSTE's rating pass (fp64 tables) in array order; *d_loss = sum(error^2)"""
+    _check(load().qrec_rste_sgd_ordered(_dp(d_P), _dp(d_Q), d, ld, _dp(d_fe_indptr), _dp(d_fe_ids), _dp(d_fe_w), _dp(d_fe_den), _dp(d_u),
+                                        _dp(d_i), _dp(d_rating), n, lr, alpha, regU, regI, _dp(d_loss), _sh(stream)))
+
+
+def social_user_pass(mode: int, d_P, d: int, ld: int, d_step_user, n_steps: int, d_fe_indptr, d_fe_ids, d_fe_w, d_fr_indptr, d_fr_ids,
+                     d_fr_w, d_order, d_level_ptr, n_levels: int, n_waves: int, lr: float, coef: float, d_slots, stream=None):
+    """the per-user social pass (SOCIAL_SOCIALMF / SOCIAL_SOREG / SOCIAL_SREE) over a level schedule"""
+    _check(load().qrec_social_user_pass(mode, _dp(d_P), d, ld, _dp(d_step_user), n_steps, _dp(d_fe_indptr), _dp(d_fe_ids), _dp(d_fe_w),
+                                        _dp(d_fr_indptr), _dp(d_fr_ids), _dp(d_fr_w), _dp(d_order), _dp(d_level_ptr), n_levels, n_waves,
+                                        lr, coef, _dp(d_slots), _sh(stream)))
+
+
+def sorec_relation_pass(d_P, d_Z, d: int, ld: int, d_rel_u, d_rel_v, d_rel_t, d_rel_w, n_rel: int, d_order, d_level_ptr, n_levels: int,
+                        n_waves: int, lr: float, regS: float, regZ: float, d_slots, stream=None):
+    """SoRec's relation pass over a level schedule"""
+    _check(load().qrec_sorec_relation_pass(_dp(d_P), _dp(d_Z), d, ld, _dp(d_rel_u), _dp(d_rel_v), _dp(d_rel_t), _dp(d_rel_w), n_rel,
+                                           _dp(d_order), _dp(d_level_ptr), n_levels, n_waves, lr, regS, regZ, _dp(d_slots), _sh(stream)))
+
+
+def loss_fold(d_running, d_slots, n: int, stream=None):
+    """*d_running += slots[0], += slots[1], ... one after the other"""
+    _check(load().qrec_loss_fold(_dp(d_running), _dp(d_slots), n, _sh(stream)))

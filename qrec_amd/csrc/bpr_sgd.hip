@@ -360,7 +360,9 @@ __global__ __launch_bounds__(64) void sbpr_ordered_kernel(
 //   VAR 3  model/rating/EE.py:15-34       diff = P[u]-Q[i]; e = r - (((mean + Bi[i]) + Bu[u]) - diff.diff);
 //                                         loss += e*e + regU*diff.diff; P[u] -= (lr*(e+regU))*diff;
 //                                         Q[i] += (lr*(e+regI))*(P[u]-Q[i]); biases as SVD
-// p is a VIEW of P[u] in the reference, so the Q[i] update sees the already updated P[u].
+//   VAR 4  model/rating/SocialMF.py:14-24 PMF's arithmetic on COPIES: p, q are taken before the updates, so the
+//                                         Q[i] update sees the old P[u]
+// p is a VIEW of P[u] in the reference (VAR 0-3), so the Q[i] update sees the already updated P[u].
 template <typename T, int EPL, int VAR>
 __global__ __launch_bounds__(64) void mf_ordered_kernel(
     T *__restrict__ P, T *__restrict__ Q, T *__restrict__ Bu, T *__restrict__ Bi, int d, int ld,
@@ -397,13 +399,17 @@ __global__ __launch_bounds__(64) void mf_ordered_kernel(
             } else if constexpr (VAR == 3) {
                 pv[e] -= (lr * (err + regU)) * (pv[e] - qv[e]);
                 qv[e] += (lr * (err + regI)) * (pv[e] - qv[e]);
+            } else if constexpr (VAR == 4) {
+                const T p0 = pv[e];
+                pv[e] += lr * (err * qv[e] - regU * p0);
+                qv[e] += lr * (err * p0 - regI * qv[e]);
             } else {
                 pv[e] += lr * (err * qv[e] - regU * pv[e]);
                 qv[e] += lr * (err * pv[e] - regI * qv[e]);
             }
             if ((lane + 64 * e) < d) { p[64 * e] = pv[e]; q[64 * e] = qv[e]; }
         }
-        if constexpr (VAR >= 2) {
+        if constexpr (VAR == 2 || VAR == 3) {
             if (lane == 0) { Bu[u] = bu + lr * (err - regB * bu); Bi[i] = bi + lr * (err - regB * bi); }
         }
     }
@@ -909,7 +915,8 @@ int dispatch_mf(int variant, void *P, void *Q, void *Bu, void *Bi, int d, int ld
         case 0: return launch_mf_ordered<T, 0>(P, Q, Bu, Bi, d, ld, u, i, r, n, lr, regU, regI, regB, gmean, loss, st);
         case 1: return launch_mf_ordered<T, 1>(P, Q, Bu, Bi, d, ld, u, i, r, n, lr, regU, regI, regB, gmean, loss, st);
         case 2: return launch_mf_ordered<T, 2>(P, Q, Bu, Bi, d, ld, u, i, r, n, lr, regU, regI, regB, gmean, loss, st);
-        default: return launch_mf_ordered<T, 3>(P, Q, Bu, Bi, d, ld, u, i, r, n, lr, regU, regI, regB, gmean, loss, st);
+        case 3: return launch_mf_ordered<T, 3>(P, Q, Bu, Bi, d, ld, u, i, r, n, lr, regU, regI, regB, gmean, loss, st);
+        default: return launch_mf_ordered<T, 4>(P, Q, Bu, Bi, d, ld, u, i, r, n, lr, regU, regI, regB, gmean, loss, st);
     }
 }
 
@@ -993,8 +1000,9 @@ int qrec_mf_sgd_ordered(void *d_P, void *d_Q, int dtype, int32_t d, int32_t ld,
     QREC_REQUIRE(n == 0 || (d_u && d_i && d_rating), "qrec_mf_sgd_ordered: null index array");
     QREC_REQUIRE(d >= 1 && d <= 256 && ld >= d, "qrec_mf_sgd_ordered: need 1 <= d <= 256, ld >= d");
     QREC_REQUIRE(dtype == QREC_F32 || dtype == QREC_F64, "qrec_mf_sgd_ordered: bad dtype %d", dtype);
-    QREC_REQUIRE(variant >= 0 && variant <= 3, "qrec_mf_sgd_ordered: variant must be 0 (BasicMF), 1 (PMF), 2 (SVD) or 3 (EE)");
-    QREC_REQUIRE(variant < 2 || (d_Bu && d_Bi), "qrec_mf_sgd_ordered: SVD and EE need the bias vectors");
+    QREC_REQUIRE(variant >= 0 && variant <= 4,
+                 "qrec_mf_sgd_ordered: variant must be 0 (BasicMF), 1 (PMF), 2 (SVD), 3 (EE) or 4 (SocialMF)");
+    QREC_REQUIRE(variant < 2 || variant > 3 || (d_Bu && d_Bi), "qrec_mf_sgd_ordered: SVD and EE need the bias vectors");
     hipStream_t st = as_stream(stream);
     if (n == 0) { QREC_HIP_CHECK(hipMemsetAsync(d_loss, 0, sizeof(double), st)); return QREC_OK; }
     return dtype == QREC_F64 ? dispatch_mf<double>(variant, d_P, d_Q, d_Bu, d_Bi, d, ld, d_u, d_i, d_rating, n, lr, regU, regI, regB, global_mean, d_loss, st)

@@ -610,6 +610,110 @@ class MfSgd:
         return self.d_Bu.numpy().astype(np.float64), self.d_Bi.numpy().astype(np.float64)
 
 
+
+class SocialSgd:
+    """The social-trust rating models on the device, order-exact, fp64 (model/rating/{SoRec,SoReg,SocialMF,RSTE,SREE}.py).
+    Holds P, Q (``tables``), Z (SoRec) or Bu/Bi (SREE), the walk of the social pass (``steps``: a social.UserSteps for
+    SocialMF / SoReg / SREE, a social.Relations for SoRec; RSTE: social.followee_csr_by_user) and its level schedule, built
+    here once.  One call per pass: ``rating_pass`` (mf_ordered_kernel -- PMF for SoRec and SoReg, SocialMF's copies,
+    EE for SREE -- or RSTE's own kernel), then ``social_pass``, which adds the pass' loss terms onto the rating loss
+    in the reference's order and returns the sum; ``sumsq_terms`` for the epoch-end regularisers."""
+    KINDS = ("SoRec", "SoReg", "SocialMF", "RSTE", "SREE")
+    _VARIANT = {"SoRec": capi.MF_PMF, "SoReg": capi.MF_PMF, "SocialMF": capi.MF_SOCIALMF, "SREE": capi.MF_EE}
+    _MODE = {"SocialMF": capi.SOCIAL_SOCIALMF, "SoReg": capi.SOCIAL_SOREG, "SREE": capi.SOCIAL_SREE}
+
+    def __init__(self, tables: DeviceTables, n: int, kind: str, steps, Z=None, Bu=None, Bi=None, schedule=None):
+        if kind not in self.KINDS:
+            raise ValueError(f"unknown social model {kind!r}")
+        if tables.dtype != np.float64:
+            raise ValueError("the social models run on fp64 tables")
+        self.t, self.n, self.kind, self.steps = tables, n, kind, steps
+        up = lambda a, dt: DeviceBuffer.from_numpy(np.ascontiguousarray(a, dtype=dt) if np.size(a) else np.zeros(1, dt))
+        if kind == "RSTE":
+            ptr, ids, w, den = steps
+            self.d_fe_ptr, self.d_fe_ids, self.d_fe_w, self.d_den = up(ptr, np.int64), up(ids, np.int32), up(w, np.float64), up(den, np.float64)
+            self.d_u = DeviceBuffer(max(n, 1), np.int32); self.d_i = DeviceBuffer(max(n, 1), np.int32)
+            self.d_r = DeviceBuffer(max(n, 1), np.float64)
+            self.d_stats = DeviceBuffer.zeros(3, np.float64)         # err^2, sum P^2, sum Q^2
+            return
+        self.mf = MfSgd(tables, n, self._VARIANT[kind], Bu, Bi)
+        self.d_stats = self.mf.d_stats
+        if kind == "SoRec":
+            self.d_Z = DeviceBuffer.from_numpy(tables._pad(np.asarray(Z, dtype=np.float64)))
+            self.d_su, self.d_sv, self.d_st, self.d_sw = up(steps.u, np.int32), up(steps.v, np.int32), up(steps.t, np.float64), up(steps.w, np.float64)
+            self.n_steps = self.n_slots = steps.n
+            self.d_zsum = DeviceBuffer.zeros(1, np.float64)
+        else:
+            self.d_user = up(steps.user, np.int32)
+            self.d_fe_ptr, self.d_fe_ids, self.d_fe_w = up(steps.fe_ptr, np.int64), up(steps.fe_ids, np.int32), up(steps.fe_w, np.float64)
+            self.d_fr_ptr = self.d_fr_ids = self.d_fr_w = None
+            if kind == "SoReg":
+                self.d_fr_ptr, self.d_fr_ids, self.d_fr_w = up(steps.fr_ptr, np.int64), up(steps.fr_ids, np.int32), up(steps.fr_w, np.float64)
+            self.n_steps = steps.n_steps
+            self.n_slots = self.n_steps if kind == "SocialMF" else int(steps.fe_ptr[-1])
+        self.d_slots = DeviceBuffer(max(self.n_slots, 1), np.float64)
+        self.set_schedule(schedule if schedule is not None else steps.schedule(tables.n_users))
+
+    def set_schedule(self, sched):
+        """run the social pass by ``sched`` (social.Schedule); social.sequential_schedule(n_steps) is the plain walk"""
+        assert sched.order.size == self.n_steps
+        self.schedule = sched
+        self.d_order = DeviceBuffer.from_numpy(np.ascontiguousarray(sched.order, dtype=np.int32) if sched.order.size else np.zeros(1, np.int32))
+        self.d_level_ptr = DeviceBuffer.from_numpy(np.ascontiguousarray(sched.level_ptr, dtype=np.int32))
+        self.n_waves = max(1, min(capi.SOCIAL_MAX_WAVES, sched.max_width))
+
+    def rating_pass(self, u, i, r, lr: float, regU: float, regI: float, regB: float = 0.0, global_mean: float = 0.0,
+                    alpha: float = 0.0, stream=None) -> float:
+        """one pass over the ratings in the given (current trainingData) order; returns its loss"""
+        if self.kind != "RSTE":
+            return self.mf.epoch(u, i, r, lr, regU, regI, regB, global_mean, stream)
+        self.d_u.upload(np.ascontiguousarray(u, dtype=np.int32), stream)
+        self.d_i.upload(np.ascontiguousarray(i, dtype=np.int32), stream)
+        self.d_r.upload(np.ascontiguousarray(r, dtype=np.float64), stream)
+        t = self.t
+        capi.rste_sgd_ordered(t.P, t.Q, t.d, t.ld, self.d_fe_ptr, self.d_fe_ids, self.d_fe_w, self.d_den, self.d_u, self.d_i, self.d_r,
+                              self.n, lr, alpha, regU, regI, self.d_stats, stream)
+        return float(self.d_stats.head(1, stream)[0])
+
+    def social_pass(self, lr: float, coef: float, regZ: float = 0.0, start: float | None = None, stream=None) -> float:
+        """the social half of the epoch (coef: regS for SoRec and SocialMF, alpha for SoReg and SREE); its loss terms are
+        added one by one in walk order onto the running loss -- the rating pass' loss, or ``start`` when given (SREE adds
+        its bias term first) -- and that sum is returned"""
+        t, s = self.t, self.schedule
+        if start is not None:
+            self.d_stats.upload_head(np.array([start], dtype=np.float64), stream)
+        if self.kind == "SoRec":
+            capi.sorec_relation_pass(t.P, self.d_Z, t.d, t.ld, self.d_su, self.d_sv, self.d_st, self.d_sw, self.n_steps, self.d_order,
+                                     self.d_level_ptr, s.n_levels, self.n_waves, lr, coef, regZ, self.d_slots, stream)
+        else:
+            capi.social_user_pass(self._MODE[self.kind], t.P, t.d, t.ld, self.d_user, self.n_steps, self.d_fe_ptr, self.d_fe_ids,
+                                  self.d_fe_w, self.d_fr_ptr, self.d_fr_ids, self.d_fr_w, self.d_order, self.d_level_ptr, s.n_levels,
+                                  self.n_waves, lr, coef, self.d_slots, stream)
+        capi.loss_fold(self.d_stats, self.d_slots, self.n_slots, stream)
+        return float(self.d_stats.head(1, stream)[0])
+
+    def sumsq_terms(self, stream=None):
+        """(sum P^2, sum Q^2, sum Z^2 or 0, sum Bu^2 or 0, sum Bi^2 or 0)"""
+        t = self.t
+        if self.kind == "RSTE":
+            capi.sumsq(t.P, t.code, t.n_users, t.d, t.ld, self.d_stats.ptr + 8, stream)
+            capi.sumsq(t.Q, t.code, t.n_items, t.d, t.ld, self.d_stats.ptr + 16, stream)
+            st = self.d_stats.numpy(stream)
+            return float(st[1]), float(st[2]), 0.0, 0.0, 0.0
+        sp, sq, sbu, sbi = self.mf.sumsq_terms(stream)
+        sz = 0.0
+        if self.kind == "SoRec":
+            capi.sumsq(self.d_Z, t.code, t.n_users, t.d, t.ld, self.d_zsum, stream)
+            sz = float(self.d_zsum.numpy(stream)[0])
+        return sp, sq, sz, sbu, sbi
+
+    def Z(self):
+        return np.ascontiguousarray(self.d_Z.numpy()[:, :self.t.d], dtype=np.float64)
+
+    def biases(self):
+        return self.mf.biases()
+
+
 class SvdppSgd:
     """SVD++ on the device, order-exact (model/rating/SVDPlusPlus.py:25-62): P, Q, the implicit-feedback table Y and
     the biases stay resident; ``rated`` = every user's train items in ``data.userRated`` order."""

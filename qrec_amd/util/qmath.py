@@ -1,8 +1,8 @@
-"""Host math helpers of the hot path (util/qmath.py:127-146)."""
+"""Host math helpers (util/qmath.py:58-76,127-146)."""
 from __future__ import annotations
 
 import heapq
-from math import exp
+from math import exp, sqrt
 
 
 def sigmoid(val: float) -> float:
@@ -22,3 +22,24 @@ def find_k_largest(K: int, candidates):
             heapq.heapreplace(heap, (score, iid))
     heap.sort(key=lambda pair: pair[0], reverse=True)
     return [iid for _, iid in heap], [score for score, _ in heap]
+
+
+def pearson_sp(x1: dict, x2: dict) -> float:
+    """Pearson correlation of two rating dicts over their common keys, each centred on its OWN full mean
+    (util/qmath.py:58-76): summed in x1's key order, squares by Python's ``** 2``; a zero denominator gives 1 when the
+    dicts overlap and 0 otherwise (so does an empty dict)."""
+    total = denom1 = denom2 = 0
+    overlapped = False
+    try:
+        mean1 = sum(x1.values()) / len(x1)
+        mean2 = sum(x2.values()) / len(x2)
+        for k in x1:
+            if k in x2:
+                a, b = x1[k] - mean1, x2[k] - mean2
+                total += a * b
+                denom1 += a ** 2
+                denom2 += b ** 2
+                overlapped = True
+        return total / (sqrt(denom1) * sqrt(denom2))
+    except ZeroDivisionError:
+        return 1 if overlapped else 0
