@@ -12,9 +12,15 @@ the bench repeats epochs inside a step until the K timed steps cover >= --min-se
 depend on that grouping (triplets / second); `ms_per_step` is per step, `config.ms_per_epoch` per epoch.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full  # + every other figure and check of the line (below)
     python bench.py --gpus N --steps K --warmup W          # N > 1 typed like this: bench.py starts its own N ranks (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what its headline figure needs and nothing else: set-up, warm-up, the K timed steps, --dump-outputs if given,
+the JSON line.  --full adds the legs that take runs of their own (marked [--full] below): CPU baselines, the order-exact mode,
+the Recall@20 comparisons with a reference, other shapes and configurations, the HBM-resident roofline, and for N > 1 the
+weak-scaling leg, the other item-table layout and config #4.  They run after the timed steps and do not change the headline.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free port>` with
@@ -27,14 +33,19 @@ N > 1, one process per GPU (qrec_amd/dist.py; collectives are RCCL bound directl
 (default): item table replicated, a delta all-reduce per reconciliation, the epoch's last one fused with the loss terms.  --dist-mode
 sharded: item table row-sharded, per batch an all-to-all of the distinct rows a rank's triplets touch and of their
 updates.  --scaling strong (default since round 4: BASELINE.json quotes the metric on THE Yelp2018 shape at 1/2/4/8 GPUs): the same
-31,668 users split over the ranks = `value`; the weak-scaling figure (every rank its own 31,668 users) is timed next to it and
+31,668 users split over the ranks = `value`; [--full] the weak-scaling figure (every rank its own 31,668 users) is timed next to it and
 reported as `weak_scaling` under its aggregate shape; --scaling weak makes that leg `value`.  --sync-per-epoch (default: 1 up to two ranks, 2 beyond):
 how often the ranks' item rows are reconciled inside an epoch.
 
 Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   roofline     -- the SGD kernel's algorithmic bytes/launch over its mean launch time (HIP events on the launch
-                  stream) against 8 TB/s HBM peak;  roofline_hbm_resident -- the same kernel on an HBM-sized problem
-                  (a single-GPU slice of BASELINE config #4: 1.25 M x 1 M, d=128, 1.15 GB of tables);
+                  stream of the timed steps) against 8 TB/s HBM peak;
+  multi_gpu    -- N > 1: what RCCL reports per rank, kernel time per rank, collectives and bytes per epoch;
+and with --full also
+  roofline_hbm_resident -- the same kernel on an HBM-sized problem (a single-GPU slice of BASELINE config #4: 1.25 M x 1 M,
+                  d=128, 1.15 GB of tables); its p_update: how the item-major kernel writes P[u] there ("rmw": sc1 load + store
+                  instead of an atomic delta, chosen by engine.resolve_p_update from the collision density;
+                  `roofline_hbm_resident_atomic` = the same slice with atomic deltas);
   exact_mode   -- the order-exact mode (the one that meets the bit-exact-stream / 1e-5 numeric contract) timed on
                   the same workload;
   cpu_baseline -- the CPU port of the same epoch (oracle/, plain C, fp64, 1 thread) timed on this box's host cores
@@ -44,11 +55,11 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                   negatives, on the bench's own graph and on the planted-community graph of the same shape (datasets[]: recall, abs_diff,
                   rel_diff at the reference's peak epoch and at the last one); N > 1: the same over the real communicator;
   other_configs -- BASELINE configs #2, #3, #5 and the evaluation, measured by this very run (HIP events, >= 20 repetitions);
-  roofline_hbm_resident.p_update -- how the item-major kernel writes P[u] there ("rmw": sc1 load + store instead of an atomic delta, chosen by
-                  engine.resolve_p_update from the collision density; `roofline_hbm_resident_atomic` = the same slice with atomic deltas);
-  multi_gpu    -- N > 1: what RCCL reports per rank, kernel time per rank, collectives and bytes per epoch.
-Sharded layout options: --shard-batch, --shard-pipeline, --no-plan-inside.  N > 1 also carries other_configs.config4_sharded:
-each rank's share of BASELINE config #4 in north_star's layout (row-sharded item table, per-batch all-to-all) and that layout's paired Recall@20.
+                  N > 1: other_configs.config4_sharded, each rank's share of BASELINE config #4 in north_star's layout (row-sharded
+                  item table, per-batch all-to-all) and that layout's paired Recall@20;
+  weak_scaling, value_sharded / value_replicated -- N > 1, strong scaling: the weak-scaling leg and the other item-table layout.
+Under --full, --no-cpu-baseline drops cpu_baseline and --no-extras every other --full leg.
+Sharded layout options: --shard-batch, --shard-pipeline, --no-plan-inside.
 Every timed region starts from a collected Python heap with the cyclic collector off (settled_heap).
 
 --dump-outputs DIR (one process only): after the timed steps, what the last step handed its caller -- the trained tables P (users x d)
@@ -577,8 +588,11 @@ def main():
     ap.add_argument("--shape", default="yelp2018")
     ap.add_argument("--min-seconds", type=float, default=0.3, help="epochs are repeated inside a step until the timed region lasts this long")
     ap.add_argument("--epochs-per-step", type=int, default=0, help="fix the inner repeat instead of calibrating it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip exact_mode / roofline_hbm_resident / recall_at_20 / other_configs / the weak-scaling leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg of the line: CPU baselines, exact_mode, recall_at_20, other_configs, "
+                         "roofline_hbm_resident; N > 1: the weak-scaling leg, the other item-table layout, config4_sharded (off: the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip exact_mode / roofline_hbm_resident / recall_at_20 / other_configs / the weak-scaling leg")
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--chunk", type=int, default=0, help="triplets per work item of the SGD kernel (0 = engine.balanced_chunk: the length in 26..40 that spreads the "
                                                          "epoch's chunks most evenly over the persistent groups)")
@@ -828,15 +842,16 @@ def main():
         return leg
 
     strong = args.scaling == "strong" and world > 1
+    extras = args.full and not args.no_extras          # the same on every rank: the N > 1 legs below are collective
     leg = run_leg(strong, args.steps, args.warmup, args.min_seconds, dump=True)
     n, CHUNK, inner, elapsed, avg_kernel_ms = leg["n"], leg["chunk"], leg["inner"], leg["elapsed"], leg["avg_kernel_ms"]
     weak_leg = None
-    if strong and not args.no_extras:       # the weak-scaling figure next to it: every rank its own U users (an N x U-user problem)
+    if strong and extras:       # the weak-scaling figure next to it: every rank its own U users (an N x U-user problem)
         weak_leg = run_leg(False, max(2, args.steps // 2), 1, args.min_seconds / 2, dump=False)
     # north_star's layout as a first-class figure of the same line: the SAME strong-scaling problem with the item table
     # row-sharded and a per-batch all-to-all -- `value_sharded` beside `value` (which runs the replicated layout unless --dist-mode says otherwise)
     other_layout_leg = None
-    if use_dist and world > 1 and strong and not args.no_extras:
+    if use_dist and world > 1 and strong and extras:
         other_layout_leg = run_leg(True, max(2, args.steps // 2), 1, args.min_seconds / 2, dump=False, layout_sharded=not sharded)
     alg_bytes = n * bytes_per_triplet(DIM)
     moved = leg["moved"]
@@ -882,7 +897,7 @@ def main():
                  "predicted_link_ms_per_epoch": predicted}
 
     recall_multi, recall_ran = None, False                # recall_multi is rank 0's; recall_ran is the same on every rank
-    if world > 1 and strong and not args.no_extras:      # every rank takes part
+    if world > 1 and strong and extras:      # every rank takes part
         ds = args.recall_dataset
         if ds == "auto":
             ds = "yelp2018-clustered" if args.shape == "yelp2018" else (args.shape if data["test_u"].size else None)
@@ -895,7 +910,7 @@ def main():
     config4 = None
     if args.config4_triplets < 0:
         args.config4_triplets = 0 if one_device else 25_000_000
-    if world > 1 and not args.no_extras and args.config4_triplets > 0:      # every rank takes part
+    if world > 1 and extras and args.config4_triplets > 0:      # every rank takes part
         scale = args.config4_triplets / 25_000_000
         config4 = config4_sharded_leg(capi, qd, control, comm, world, rank, args.shard_batch, qd.reconciliations_per_epoch(world, args.sync_per_epoch),
                                       users=max(1000, int(1_250_000 * scale)), items=max(1000, int(1_000_000 * scale)), triplets=args.config4_triplets)
@@ -987,11 +1002,11 @@ def main():
         if config4 is not None:
             out.setdefault("other_configs", {})["config4_sharded"] = config4
         if world == 1 and not use_dist:
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(u, items, indptr, I, U)
                 out["vs_cpu_port"] = value / out["cpu_baseline"]["value"]
                 out["vs_reference_loop_here"] = value / out["cpu_baseline"]["reference_loop_here"]["value"]
-            if not args.no_extras:
+            if extras:
                 out["recall_at_20"] = recall_legs(args.schedule, args.shape)
                 out["exact_mode"] = exact_mode_rate(capi, u, items, indptr, I, leg["P0"], Q0)
                 # the HBM-resident slice of config #4 (1.15 GB of tables: real HBM traffic) under what `auto` resolves to at that size: item-major,

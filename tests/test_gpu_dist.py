@@ -470,7 +470,7 @@ def test_bench_typed_with_gpus_2_starts_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(QREC_DIST_TEST_ONE_DEVICE="1", QREC_DIST_TEST_DUMP=str(tmp_path), QREC_DIST_MODE="replicated")
     env.pop("QREC_SCALING", None)            # the default answers BASELINE.json's question: the ONE problem over N GPUs
-    run = subprocess.run(["python3", "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--epochs-per-step", "2", "--no-cpu-baseline",
+    run = subprocess.run(["python3", "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--epochs-per-step", "2", "--full", "--no-cpu-baseline",
                           "--shape", "ml1m", "--recall-dataset", "lastfm", "--recall-epochs", "10", "--config4-triplets", "150000"], cwd=ROOT, env=env, capture_output=True, text=True,
                          timeout=900)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-3000:]
@@ -485,7 +485,7 @@ def test_bench_typed_with_gpus_2_starts_its_own_ranks(tmp_path):
     assert sum(mg["triplets_per_epoch_per_rank"]) == out["config"]["triplets_per_epoch_per_gpu"] + mg["triplets_per_epoch_per_rank"][1]
     assert mg["collectives_per_epoch"]["all_reduce"] == 1 and mg["collectives_per_epoch"]["payload_bytes_per_rank"] > 3706 * 64 * 4    # two ranks: the epoch close's fused all-reduce alone (dist.reconciliations_per_epoch)
     assert (tmp_path / "rank0.npz").exists() and (tmp_path / "rank1.npz").exists()
-    # round 4: strong scaling is the default and the workload string says what is being scaled; the weak-scaling figure stands next
+    # round 4: strong scaling is the default and the workload string says what is being scaled; with --full, the weak-scaling figure stands next
     # to it under its aggregate shape; the collectives' bytes come with the link-time arithmetic; and the metric's second half --
     # Recall@20 against order-exact training of the whole problem, trained through this very communicator -- is on the line
     assert "strong scaling" in out["config"]["workload"] and "6040x3706" in out["config"]["workload"]
@@ -533,6 +533,19 @@ def test_two_rank_bench_path_with_row_sharded_item_table(tmp_path, scaling):
     assert r0["log"][-1, 0] < r0["log"][0, 0]
     Q0 = (np.random.default_rng(999).random((I, 64)) / 3).astype(np.float32)
     assert (np.abs(r0["Q"][:, :64] - Q0[0::2]).max(1) > 0).mean() > 0.99 and (np.abs(r1["Q"][:, :64] - Q0[1::2]).max(1) > 0).mean() > 0.99
+
+
+def test_plain_bench_line_is_the_headline_alone():
+    """`bench.py` without --full: the contract fields, the timed leg's config and roofline, and none of the legs that take runs of
+    their own (they come with --full, checked through test_bench_typed_with_gpus_2_starts_its_own_ranks)."""
+    out = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--epochs-per-step", "3", "--shape", "ml1m"], {}, timeout=300)
+    assert out["metric"] == "BPR triplet-updates/sec" and out["unit"] == "triplet-updates/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(out["config"]["triplets_per_epoch_job"] * 3 / (out["ms_per_step"] * 1e-3))
+    assert out["config"]["epochs_per_step"] == 3 and out["roofline"]["avg_launch_ms"] > 0
+    moved = ("cpu_baseline", "vs_cpu_port", "vs_reference_loop_here", "recall_at_20", "exact_mode", "roofline_hbm_resident",
+             "roofline_hbm_resident_atomic", "other_configs", "weak_scaling", "value_sharded", "value_replicated")
+    assert not [k for k in moved if k in out]
 
 
 @pytest.mark.parametrize("mode", ["replicated", "sharded"])

@@ -6,7 +6,7 @@
 # steps
 #   tests[:expr]         pytest -m gpu (optionally -k expr), parity ledger into gpurun_out/<tag>_parity_raw.jsonl
 #   tests-all[:expr]     the same without -x (every failure of the selection in one call), ledger into <tag>_parity_all_raw.jsonl
-#   bench                python bench.py (default flags) -> <tag>_bench.json
+#   bench                python bench.py --full (every leg of the line) -> <tag>_bench.json
 #   bench-prof           bench + rocprofv3 --kernel-trace --stats + the two HBM counter passes (separate) + tools/summarize_prof.py
 #   recall:<plan>        tools/paired_recall.py <tag>_recall_<plan>.json <plan>       (plan: bpr-conf | full | quick | a JSON file under tools/plans/)
 #   spmm-counters        FETCH_SIZE / WRITE_SIZE (separate passes) of the forward SpMM on the structureless and the planted-community graph
@@ -47,7 +47,7 @@ for STEP in "$@"; do
       grep -E "^(FAILED|ERROR)|passed|failed" $O/${TAG}_tests_all.log | cut -c1-300 | tail -40
       cd /tmp;;
     bench)
-      timeout 900 python $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "bench exit $?"; head -c 1500 $O/${TAG}_bench.json; echo;;
+      timeout 900 python $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "bench exit $?"; head -c 1500 $O/${TAG}_bench.json; echo;;
     bench-prof)
       bash $R/tools/run_bench_prof.sh $TAG;;
     recall)
