@@ -750,6 +750,48 @@ int qrec_als_solve_rows(const double *d_F, int64_t f_rows, const double *d_G, do
                         const int64_t *d_indptr, const int32_t *d_indices, const double *d_c, double lambda, double *d_loss,
                         void *d_ws, int64_t ws_bytes, void *stream);
 
+/* ---- exposure-weighted ALS, fp64 (model/ranking/ExpoMF.py, model/ranking/SERec.py; exposure.hip) --------------------- *
+ * Tables as for ALS: fp64 [rows][ld], ld in {16, 32, 64, 128}, 1 <= d <= ld, pad columns zero; d > QREC_ALS_MAX_D returns
+ * QREC_ERR_UNSUPPORTED.  The exposure posterior of (row r, column c), from the row's table X and the column's table F:
+ *     pEX = sqrt(lam_y / 2 pi) exp(-lam_y (X[r] . F[c])^2 / 2),   A_rc = (pEX + 1e-8) / (pEX + 1e-8 + (1 - mu_rc) / mu_rc)
+ * with the prior mu_rc given by qrec_expo_prior_t:
+ *   QREC_EXPO_PRIOR_COL           mu_rc = v[c]                    (ExpoMF, user half)
+ *   QREC_EXPO_PRIOR_ROW           mu_rc = v[r]                    (ExpoMF, item half)
+ *   QREC_EXPO_PRIOR_SOCIAL_T_ROW  mu_rc = m(t[r], a_sum[c])       (SERec, user half)
+ *   QREC_EXPO_PRIOR_SOCIAL_T_COL  mu_rc = m(t[c], a_sum[r])       (SERec, item half)
+ *   m(t, A) = (a + A + (s - 1) t A - 1) / (a + b + (s - 1) t A + n_users - 2)   (SERec.py:92-95; T.dot(tile(A_sum)) = t_u A_i)
+ * qrec_expo_solve_rows: for every row r of X (its observed columns: d_indptr[n_rows + 1] / d_indices, unique within a row)
+ *       B_r = sum_{c < n_cols} A_rc F[c] F[c]^T + lambda I   with A_rc = 1 on the observed columns,
+ *       b_r = sum_{c observed} F[c],   X[r] = B_r^-1 b_r   (Cholesky; A from X's rows before this call)
+ *   on f64 MFMA, every sum in a fixed order (bit-reproducible).  X is written only when every row succeeded: a non-positive
+ *   (or NaN) pivot returns QREC_ERR_NOT_SPD, an index outside [0, n_cols) or a decreasing indptr QREC_ERR_INVALID, and X
+ *   is left as it was.  Waits for its stream.  Workspace: qrec_expo_solve_workspace_bytes.
+ * qrec_expo_prior: the prior pass over rows = users (X, n_rows) and columns = items (F, n_cols), the columns' observed rows
+ *   given by d_col_indptr / d_col_indices:  d_a_sum[c] = sum_r A_rc (A = 1 on observed pairs), summed over a fixed
+ *   partition of the rows in a fixed order; when d_mu is not NULL also d_mu[c] = (a + A_c - 1) / (a + b + n_users - 2)
+ *   (ExpoMF.py:73).  d_a_sum / d_mu may alias the prior's own vectors (they are written after every read).  Nothing is
+ *   written on QREC_ERR_INVALID.  Waits for its stream.  Workspace: qrec_expo_prior_workspace_bytes. */
+#define QREC_EXPO_PRIOR_COL 0
+#define QREC_EXPO_PRIOR_ROW 1
+#define QREC_EXPO_PRIOR_SOCIAL_T_ROW 2
+#define QREC_EXPO_PRIOR_SOCIAL_T_COL 3
+typedef struct {
+    int32_t mode;
+    int32_t reserved;
+    const double *v;       /* modes COL / ROW */
+    const double *t;       /* social modes: followee counts per user */
+    const double *a_sum;   /* social modes: A_sum per item */
+    double a, b, s, n_users, lam_y;
+} qrec_expo_prior_t;
+int qrec_expo_solve_workspace_bytes(int64_t n_rows, int32_t ld, int64_t *bytes);
+int qrec_expo_solve_rows(const double *d_F, int64_t n_cols, double *d_X, int64_t n_rows, int32_t d, int32_t ld,
+                         const int64_t *d_indptr, const int32_t *d_indices, const qrec_expo_prior_t *prior, double lambda,
+                         void *d_ws, int64_t ws_bytes, void *stream);
+int qrec_expo_prior_workspace_bytes(int64_t n_rows, int64_t n_cols, int64_t *bytes);
+int qrec_expo_prior(const double *d_X, int64_t n_rows, const double *d_F, int64_t n_cols, int32_t d, int32_t ld,
+                    const int64_t *d_col_indptr, const int32_t *d_col_indices, const qrec_expo_prior_t *prior, double *d_a_sum,
+                    double *d_mu, void *d_ws, int64_t ws_bytes, void *stream);
+
 /* ---- memory-based rating models, fp64 (model/rating/{UserKNN,ItemKNN,SlopeOne}.py, util/qmath.py:19-115; knn.hip) ----- *
  * No FMA contraction; every sum runs in the reference's order; no float atomics: a run is bit-identical to the next.
  * qrec_knn_sweep: for every query t < n_queries (its row: d_q_keys / d_q_vals[d_q_indptr[t] .. d_q_indptr[t + 1]), in the

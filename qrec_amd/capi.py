@@ -154,6 +154,10 @@ _SIGNATURES = {
     "qrec_als_gram": [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp],
     "qrec_als_solve_workspace_bytes": [_vp, _i64, _i32, _vp],
     "qrec_als_solve_rows": [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _f64, _vp, _vp, _i64, _vp],
+    "qrec_expo_solve_workspace_bytes": [_i64, _i32, _vp],
+    "qrec_expo_solve_rows": [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _f64, _vp, _i64, _vp],
+    "qrec_expo_prior_workspace_bytes": [_i64, _i64, _vp],
+    "qrec_expo_prior": [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "qrec_knn_sweep": [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp],
     "qrec_knn_topk_workspace_bytes": [_i64, _i64, _vp],
     "qrec_knn_topk": [_i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
@@ -1247,6 +1251,48 @@ def als_solve_rows(d_F, f_rows: int, d_G, d_X, n_rows: int, d: int, ld: int, d_i
     ERR_NOT_SPD when a system is not positive definite (X untouched)."""
     _check(load().qrec_als_solve_rows(_dp(d_F), f_rows, _dp(d_G), _dp(d_X), n_rows, d, ld, _dp(d_indptr), _dp(d_indices), _dp(d_c),
                                       lam, _dp(d_loss), _dp(d_ws), ws_bytes, _sh(stream)))
+
+
+# ---- exposure-weighted ALS (exposure.hip) ---------------------------------------------------------------------------------
+EXPO_PRIOR_COL, EXPO_PRIOR_ROW, EXPO_PRIOR_SOCIAL_T_ROW, EXPO_PRIOR_SOCIAL_T_COL = 0, 1, 2, 3
+
+
+class ExpoPrior(C.Structure):
+    """qrec_expo_prior_t: which prior mu_rc the posterior uses (see include/qrec_hip.h)"""
+    _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32), ("v", C.c_void_p), ("t", C.c_void_p), ("a_sum", C.c_void_p),
+                ("a", C.c_double), ("b", C.c_double), ("s", C.c_double), ("n_users", C.c_double), ("lam_y", C.c_double)]
+
+
+def expo_prior_desc(mode: int, lam_y: float, v=None, t=None, a_sum=None, a: float = 1.0, b: float = 99.0, s: float = 1.0,
+                    n_users: int = 0) -> ExpoPrior:
+    return ExpoPrior(mode, 0, _dp(v), _dp(t), _dp(a_sum), a, b, s, float(n_users), lam_y)
+
+
+def expo_solve_workspace_bytes(n_rows: int, ld: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_expo_solve_workspace_bytes(n_rows, ld, C.byref(out)))
+    return out.value
+
+
+def expo_solve_rows(d_F, n_cols: int, d_X, n_rows: int, d: int, ld: int, d_indptr, d_indices, prior: ExpoPrior, lam: float, d_ws,
+                    ws_bytes: int, stream=None):
+    """X[r] = (sum_c A_rc f_c f_c^T + lam I)^-1 sum_{c observed} f_c for every row (A from X's rows before the call); waits
+    for the stream.  QRecError ERR_NOT_SPD / ERR_INVALID / ERR_UNSUPPORTED leave X untouched."""
+    _check(load().qrec_expo_solve_rows(_dp(d_F), n_cols, _dp(d_X), n_rows, d, ld, _dp(d_indptr), _dp(d_indices), C.byref(prior), lam,
+                                       _dp(d_ws), ws_bytes, _sh(stream)))
+
+
+def expo_prior_workspace_bytes(n_rows: int, n_cols: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_expo_prior_workspace_bytes(n_rows, n_cols, C.byref(out)))
+    return out.value
+
+
+def expo_prior(d_X, n_rows: int, d_F, n_cols: int, d: int, ld: int, d_col_indptr, d_col_indices, prior: ExpoPrior, d_a_sum, d_mu,
+               d_ws, ws_bytes: int, stream=None):
+    """a_sum[c] = sum_r A_rc (A = 1 on observed pairs); mu[c] = ExpoMF's prior from it when d_mu is given.  Waits for the stream."""
+    _check(load().qrec_expo_prior(_dp(d_X), n_rows, _dp(d_F), n_cols, d, ld, _dp(d_col_indptr), _dp(d_col_indices), C.byref(prior),
+                                  _dp(d_a_sum), _dp(d_mu), _dp(d_ws), ws_bytes, _sh(stream)))
 
 
 # ---- memory-based rating models (knn.hip) -----------------------------------------------------------------------------------

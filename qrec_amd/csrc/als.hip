@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <climits>
 
+#include "chol_lds.h"
 #include "common.h"
 
 using namespace qrec;
@@ -23,13 +24,6 @@ constexpr int kGramRowsPerBlock = 256;
 constexpr int kGramMaxBlocks = 256;
 
 enum Status { kOk = 0, kNotSpd = 1, kWorkspace = 2, kBadIndex = 3, kBadIndptr = 4 };
-
-__device__ inline double readlane_f64(double v, int lane) {
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
 
 // One block accumulates  acc += sum_k c_k f_k f_k^T,  bacc (thread tid < ld: column tid) += sum_k (1 + c_k) f_k,
 // loss (thread 0) += sum_k (1 - x_old . f_k)^2  over neighbours k in [beg, end) (rows idx[k] of F, or rows k when idx is
@@ -277,40 +271,13 @@ __global__ __launch_bounds__(kThreads) void als_solve_kernel(const double *__res
     if (tid < ld) s_b[tid] = bacc;
     if (tid == 0 && with_loss) w.row_loss[r] = loss;
     __syncthreads();
-    // Cholesky, right-looking: L overwrites the strict lower triangle, the diagonal goes to s_diag
-    for (int k = 0; k < d; ++k) {
-        const double piv = A[k * lda + k];
-        if (!(piv > 0.0)) {                       // uniform over the block: every thread read the same pivot
-            if (tid == 0) { atomicCAS(w.status, kOk, kNotSpd); atomicMin(w.status + 1, (int)r); }
-            return;
-        }
-        const double lkk = sqrt(piv);
-        if (tid == 0) s_diag[k] = lkk;
-        for (int i = k + 1 + tid; i < d; i += kThreads) A[i * lda + k] = A[i * lda + k] / lkk;
-        __syncthreads();
-        for (int i = k + 1 + ty; i < d; i += 16) {
-            const double lik = A[i * lda + k];
-            for (int j = k + 1 + tx; j <= i; j += 16) A[i * lda + j] = fma(-lik, A[j * lda + k], A[i * lda + j]);
-        }
-        __syncthreads();
+    // Cholesky (chol_lds.h): L overwrites the strict lower triangle, the diagonal goes to s_diag
+    if (!chol_factor_lds(A, lda, d, s_diag)) {
+        if (tid == 0) { atomicCAS(w.status, kOk, kNotSpd); atomicMin(w.status + 1, (int)r); }
+        return;
     }
     if (tid >= 64) return;
-    // L y = b, then L^T x = y; lane l holds entries l and l + 64
-    const int i0 = tid, i1 = tid + 64;
-    double v0 = i0 < d ? s_b[i0] : 0.0, v1 = i1 < d ? s_b[i1] : 0.0;
-    for (int k = 0; k < d; ++k) {
-        const double yk = readlane_f64(k < 64 ? v0 : v1, k & 63) / s_diag[k];
-        if (i0 > k && i0 < d) v0 = fma(-A[i0 * lda + k], yk, v0); else if (i0 == k) v0 = yk;
-        if (i1 > k && i1 < d) v1 = fma(-A[i1 * lda + k], yk, v1); else if (i1 == k) v1 = yk;
-    }
-    for (int k = d - 1; k >= 0; --k) {
-        const double xk = readlane_f64(k < 64 ? v0 : v1, k & 63) / s_diag[k];
-        if (i0 < k) v0 = fma(-A[k * lda + i0], xk, v0); else if (i0 == k) v0 = xk;
-        if (i1 < k) v1 = fma(-A[k * lda + i1], xk, v1); else if (i1 == k) v1 = xk;
-    }
-    double *out = w.x_new + r * ld;
-    if (i0 < ld) out[i0] = i0 < d ? v0 : 0.0;
-    if (i1 < ld) out[i1] = i1 < d ? v1 : 0.0;
+    chol_solve_wave(A, lda, d, ld, s_b, s_diag, w.x_new + r * ld);
 }
 
 // The solutions into the table, the loss partials into one sum (fixed order) -- only when every row succeeded.

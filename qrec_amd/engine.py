@@ -802,6 +802,92 @@ class AlsSolver:
         return self.t.download(np.float64)
 
 
+
+def _csr_by(rows: np.ndarray, cols: np.ndarray, n_rows: int):
+    """(indptr int64, indices int32) of the pairs grouped by row, columns ascending within a row"""
+    order = np.lexsort((cols, rows))
+    indptr = np.zeros(n_rows + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=n_rows), out=indptr[1:])
+    return indptr, np.ascontiguousarray(cols[order], dtype=np.int32)
+
+
+class ExposureSolver:
+    """Exposure-weighted ALS (model/ranking/ExpoMF.py, model/ranking/SERec.py) with everything resident on the device: theta
+    (users) and beta (items) in one fp64 ``DeviceTables`` (P = theta, Q = beta), the observed pairs by user and by item, the
+    prior state and the workspaces.  ``epoch()`` solves every user's row, then every item's row against the new theta, then
+    updates the prior with the new tables (the old prior enters that pass's posterior).
+
+    The prior: ExpoMF keeps one mu per item.  SERec (``t`` given: followee counts per user) starts from the constant
+    ``mu0`` and afterwards keeps ``A_sum`` per item; mu[u, i] = m(t[u], A_sum[i]) is formed inside the kernels, so no
+    users x items array exists.  The reference picks the item half's prior branch by comparing sizes (ExpoMF.py:104,
+    SERec.py:141); with as many users as items it takes the user branch for the items too, and so does this class.
+    Every sum has a fixed order: two runs from the same state are bit-identical."""
+
+    def __init__(self, theta: np.ndarray, beta: np.ndarray, uid: np.ndarray, iid: np.ndarray, lam: float, lam_y: float,
+                 mu0: float = float(np.float32(0.01)), a: float = 1.0, b: float = 99.0, s: float = 2.2, t: np.ndarray | None = None):
+        self.n_users, self.n_items = theta.shape[0], beta.shape[0]
+        self.t = DeviceTables(theta, beta, np.float64)
+        self.d, self.ld, self.lam, self.lam_y = self.t.d, self.t.ld, float(lam), float(lam_y)
+        self.a, self.b, self.s = float(a), float(b), float(s)
+        u = np.asarray(uid, dtype=np.int64); i = np.asarray(iid, dtype=np.int64)
+        self.by_user = [DeviceBuffer.from_numpy(x) for x in _csr_by(u, i, self.n_users)]
+        self.by_item = [DeviceBuffer.from_numpy(x) for x in _csr_by(i, u, self.n_items)]
+        self.social = t is not None
+        self.d_mu = DeviceBuffer.from_numpy(np.full(self.n_items, mu0, dtype=np.float64))
+        self.d_t = DeviceBuffer.from_numpy(np.ascontiguousarray(t, dtype=np.float64)) if self.social else None
+        self.d_asum = DeviceBuffer.zeros((max(self.n_items, 1),), np.float64)
+        self.has_asum = False           # SERec: mu is the constant mu0 until the first prior update
+        self.ws_bytes = max(capi.expo_solve_workspace_bytes(self.n_users, self.ld), capi.expo_solve_workspace_bytes(self.n_items, self.ld))
+        self.d_ws = DeviceBuffer((self.ws_bytes,), np.uint8)
+        self.prior_ws_bytes = capi.expo_prior_workspace_bytes(self.n_users, self.n_items)
+        self.d_prior_ws = DeviceBuffer((self.prior_ws_bytes,), np.uint8)
+
+    def _prior(self, half: str):
+        """the prior descriptor of a pass: half in ("user", "item", "expo")"""
+        same = self.n_users == self.n_items              # the reference's size test picks the user branch (see the class doc)
+        if self.social and self.has_asum:
+            mode = capi.EXPO_PRIOR_SOCIAL_T_COL if half == "item" and not same else capi.EXPO_PRIOR_SOCIAL_T_ROW
+        else:
+            mode = capi.EXPO_PRIOR_ROW if half == "item" and not same else capi.EXPO_PRIOR_COL
+        return capi.expo_prior_desc(mode, self.lam_y, v=self.d_mu, t=self.d_t, a_sum=self.d_asum, a=self.a, b=self.b, s=self.s,
+                                    n_users=self.n_users)
+
+    def half(self, side: int, stream=None):
+        """side 0: every user's row of theta against beta; 1: every item's row of beta against theta"""
+        F, X, n_cols, n_rows, csr = ((self.t.Q, self.t.P, self.n_items, self.n_users, self.by_user) if side == 0 else
+                                     (self.t.P, self.t.Q, self.n_users, self.n_items, self.by_item))
+        capi.expo_solve_rows(F, n_cols, X, n_rows, self.d, self.ld, csr[0], csr[1], self._prior("user" if side == 0 else "item"),
+                             self.lam, self.d_ws, self.ws_bytes, stream)
+
+    def update_prior(self, stream=None):
+        """A_sum[i] = sum_u A_ui with the new tables and the old prior; ExpoMF's mu, or SERec's A_sum, from it"""
+        capi.expo_prior(self.t.P, self.n_users, self.t.Q, self.n_items, self.d, self.ld, self.by_item[0], self.by_item[1],
+                        self._prior("expo"), self.d_asum, None if self.social else self.d_mu, self.d_prior_ws, self.prior_ws_bytes,
+                        stream)
+        self.has_asum = True
+
+    def epoch(self, stream=None):
+        self.half(0, stream)
+        self.half(1, stream)
+        self.update_prior(stream)
+
+    def prior_state(self):
+        """ExpoMF: mu per item.  SERec: (t per user, A_sum per item), or (t, None) while mu is still the constant mu0."""
+        if not self.social:
+            return self.d_mu.numpy()[:self.n_items].copy()
+        return self.d_t.numpy().copy(), (self.d_asum.numpy()[:self.n_items].copy() if self.has_asum else None)
+
+    def download(self):
+        """(theta, beta, prior) as fp64 host arrays; prior as in ``prior_state``"""
+        theta, beta = self.t.download(np.float64)
+        return theta, beta, self.prior_state()
+
+
+def serec_mu(t: np.ndarray, a_sum: np.ndarray, n_users: int, a: float = 1.0, b: float = 99.0, s: float = 2.2) -> np.ndarray:
+    """SERec's prior mu[u, i] for the users t covers (SERec.py:92-95, T.dot(tile(A_sum)) = t_u A_i): [len(t), len(a_sum)]"""
+    S = np.asarray(t, dtype=np.float64)[:, None] * np.asarray(a_sum, dtype=np.float64)[None, :]
+    return (a + a_sum[None, :] + (s - 1) * S - 1) / (a + b + (s - 1) * S + n_users - 2)
+
 def _take_rows(csr: CSR, rows: np.ndarray):
     """(indptr, indices, values) of the CSR's rows ``rows`` (-1: an empty row), in that order"""
     rows = np.asarray(rows, dtype=np.int64)
