@@ -1023,3 +1023,73 @@ def test_paired_recall_harness_host_logic():
             assert {(ds, lr0, "item", w, l) for w in (2, 4) for l in ("replicated", "sharded")} <= keys
     assert PR.parse_mode("item") == ("item", "atomic") and PR.parse_mode("item:rmw") == ("item", "rmw") and PR.parse_mode("user") == ("user", "atomic")
     assert PR.parse_mode("item-deferred:4:fresh") == ("item", "atomic")           # a mode of rounds 3-5's result files: its stored order
+
+
+# ---------------------------------------------------------------------------------------------
+# conflict-free triplet lists (tests/conflict_free.py): what the full-grid tests of the throughput kernels rest on
+# ---------------------------------------------------------------------------------------------
+def _item_major_stored_order(u, i, j, item_run):
+    """BprSgd's item-major stored order (qrec_amd/engine.py): stable sort by positive item, then runs of ``item_run`` in stride order"""
+    from qrec_amd.engine import stride_runs
+    perm = np.argsort(i, kind="stable")
+    if item_run > 0 and i.size > item_run:
+        perm = perm[stride_runs(i.size, item_run)]
+    return tuple(np.ascontiguousarray(x[perm]) for x in (u, i, j))
+
+
+_CF_COMBOS = [(64, 0, 64, 0), (16, 16, 32, 0), (16, 16, 32, 5), (32, 0, 32, 7), (7, 7, 7, 3), (16, 16, 64, 9), (8, 8, 32, 0), (8, 8, 8, 3)]
+
+
+@pytest.mark.parametrize("block,item_run,chunk,tail", _CF_COMBOS)
+def test_conflict_free_generator_gives_row_disjoint_chunks_in_the_stored_order(block, item_run, chunk, tail):
+    from conflict_free import chunks_are_row_disjoint, conflict_free_triplets
+    n_blocks, nu, ni = 9001, 5, 12
+    u, i, j = conflict_free_triplets(np.random.default_rng(block + tail), n_blocks, block, nu, ni, tail)
+    assert u.size == (n_blocks - 1) * block + (tail or block) and u.dtype == i.dtype == j.dtype == np.int32
+    b = np.arange(u.size) // block
+    assert np.array_equal(u // nu, b) and np.array_equal(i // ni, b) and np.array_equal(j // ni, b)
+    assert (i % ni < ni // 2).all() and (j != i).all() and (j % ni < ni // 2).any() and (j % ni >= ni // 2).any()
+    # the aliasing the kernels' forwarding paths need is there, inside the blocks: the same user and the same negative two triplets apart,
+    # a negative that is the previous triplet's positive, a negative that is a later positive
+    assert (u[2:] == u[:-2]).any() and (j[2:] == j[:-2]).any() and (j[1:] == i[:-1]).any() and (j[:-1] == i[1:]).any()
+    # user-major kernel: the stored order is the given one, a chunk is a block
+    assert chunks_are_row_disjoint(u, i, j, block)
+    # item-major kernel: the order BprSgd stores
+    us, is_, js = _item_major_stored_order(u, i, j, item_run)
+    assert chunks_are_row_disjoint(us, is_, js, chunk)
+
+
+def test_row_disjoint_check_sees_planted_conflicts():
+    from conflict_free import chunks_are_row_disjoint, conflict_free_triplets
+    u, i, j = conflict_free_triplets(np.random.default_rng(1), 50, 16, 5, 12, 5)
+    assert chunks_are_row_disjoint(u, i, j, 16) and chunks_are_row_disjoint(u, i, j, 32)
+    x = u.copy(); x[40] = u[3]                                   # one user of block 0 in block 2
+    assert not chunks_are_row_disjoint(x, i, j, 16)
+    x = j.copy(); x[100] = j[3]                                  # one negative of block 0 in block 6
+    assert not chunks_are_row_disjoint(u, i, x, 16)
+    x = j.copy(); x[100] = i[3]                                  # ... a negative that is another block's positive
+    assert not chunks_are_row_disjoint(u, i, x, 16)
+    assert not chunks_are_row_disjoint(u, i, j, 8) and not chunks_are_row_disjoint(u, i, j, 24)      # chunks that cut the blocks
+    us, is_, js = _item_major_stored_order(u, i, j, 8)          # runs of 8 deal a block of 16 to two chunks
+    assert not chunks_are_row_disjoint(us, is_, js, 16)
+
+
+@pytest.mark.parametrize("block,item_run,chunk,tail", [(16, 16, 32, 5), (32, 0, 32, 7), (7, 7, 7, 3)])
+def test_oracle_on_row_disjoint_chunks_does_not_depend_on_the_chunk_order(block, item_run, chunk, tail):
+    """the property the GPU tests lean on: with row-disjoint chunks the recurrence gives the SAME tables, bit for bit, whatever order the
+    chunks are visited in.  The loss is one sum over all triplets: another order of the same terms, so it is held to 1e-12, not equality."""
+    from conflict_free import chunks_are_row_disjoint, chunks_in_order, conflict_free_triplets
+    rng = np.random.default_rng(chunk)
+    n_blocks, nu, ni, d = 2001, 5, 12, 20
+    us, is_, js = _item_major_stored_order(*conflict_free_triplets(rng, n_blocks, block, nu, ni, tail), item_run)
+    assert chunks_are_row_disjoint(us, is_, js, chunk)
+    P0 = rng.random((n_blocks * nu + 3, d)) / 3; Q0 = rng.random((n_blocks * ni + 3, d)) / 3
+    Pa, Qa = P0.copy(), Q0.copy()
+    la = O.bpr_sgd(Pa, Qa, us, is_, js, 0.05, 0.01, 0.02)
+    order = chunks_in_order(us.size, chunk, rng.permutation(-(-us.size // chunk)))
+    assert np.array_equal(np.sort(order), np.arange(us.size)) and not np.array_equal(order, np.arange(us.size))
+    Pb, Qb = P0.copy(), Q0.copy()
+    lb = O.bpr_sgd(Pb, Qb, np.ascontiguousarray(us[order]), np.ascontiguousarray(is_[order]), np.ascontiguousarray(js[order]), 0.05, 0.01, 0.02)
+    assert np.array_equal(Pa, Pb) and np.array_equal(Qa, Qb)
+    assert abs(la - lb) <= 1e-12 * abs(la)
+    assert np.array_equal(Pa[-3:], P0[-3:]) and np.array_equal(Qa[-3:], Q0[-3:]) and not np.array_equal(Pa[:-3], P0[:-3])
