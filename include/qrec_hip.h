@@ -750,6 +750,50 @@ int qrec_als_solve_rows(const double *d_F, int64_t f_rows, const double *d_G, do
                         const int64_t *d_indptr, const int32_t *d_indices, const double *d_c, double lambda, double *d_loss,
                         void *d_ws, int64_t ws_bytes, void *stream);
 
+/* ---- CoFactor, fp64 (model/ranking/CoFactor.py; cofactor.hip) ---------------------------------------------------------- *
+ * Co-occurrence (CoFactor.py:36-56).  The binary rating matrix as two CSR views: d_i_indptr[n_items + 1] / d_i_users[i_nnz] (the
+ * raters of every item) and d_u_indptr[n_users + 1] / d_u_items[u_nnz] (every user's items, ascending, no duplicates).
+ * count(i, j) = the users who rated both; the pair (i, j), i != j, is kept when count > filter and both items have >= filter
+ * raters (filter >= 0).  Integer arithmetic throughout: the result does not depend on any order.
+ * qrec_cooc_count: *kept = the number of kept directed pairs (both (i, j) and (j, i) count); leaves the per-(item, tile)
+ *   offsets in the workspace for qrec_cooc_fill.  Waits for its stream.  Workspace: qrec_cooc_workspace_bytes.
+ * qrec_cooc_fill: after qrec_cooc_count of the same inputs and workspace, the kept pairs as a CSR: d_out_indptr[n_items + 1],
+ *   d_out_cols / d_out_counts[capacity], columns ascending within a row.  More kept pairs than capacity: QREC_ERR_INVALID and
+ *   nothing written.  Waits for its stream.
+ * An index outside its table or an indptr that decreases or passes its nnz returns QREC_ERR_INVALID (the outputs are then undefined
+ * but every access stayed in bounds).
+ *
+ * Item step (CoFactor.py:116-159).  Tables as for ALS: fp64 [rows][ld], ld in {16, 32, 64, 128}, 1 <= d <= ld, pad columns zero;
+ * d_w, d_c fp64 [n_items].  d_XtX = X^T X (qrec_als_gram).  Ratings by item: d_r_indptr[n_items + 1], d_r_users, d_r_conf[r_nnz].
+ * Contexts by item: d_s_indptr[n_items + 1], d_s_items, d_s_vals[s_nnz] (the SPPMI rows, in the order their sums are to be
+ * taken).  For item i with contexts k, s = its value, from the rows as they are when the step runs:
+ *     Y[i] = (XtX + sum_u conf x x^T + lambda I + sum_k g_k g_k^T)^-1 (sum_u (1 + conf) x + sum_k (s - w_i - c_k) g_k)
+ *     G[i] = (sum_k y_k y_k^T + gamma I)^-1 sum_k (s - w_k - c_i) y_k
+ *     w[i] = mean_k (s - Y_old[i] . g_k - c_k),   c[i] = mean_k (s - y_k . G_old[i] - w_k)
+ * (Cholesky; w_i, c_i in the sums are the old values).  d_order[h_level_ptr[n_levels]] lists the items with contexts level by
+ * level (h_level_ptr on the host): the items of one level must not be contexts of one another; the levels run in order, one
+ * launch each, so a step sees the rows written by the earlier levels -- with level(i) = 1 + max level(earlier context) this is
+ * the reference's sequential sweep.  d_solo[n_solo] lists the items without contexts, solved as plain ALS rows (only Y[i]
+ * changes); items in neither list are left alone.  Every sum has a fixed order: bit-reproducible.  The sweep runs on copies
+ * of Y, G, w, c in the workspace, copied back only when every system was positive definite: QREC_ERR_NOT_SPD (naming the
+ * smallest failing item), an index outside its table or a bad indptr (QREC_ERR_INVALID) leave all four as they were.  Waits for
+ * its stream.  Workspace: qrec_cofactor_item_workspace_bytes(n_items, number of scheduled items, ld). */
+#define QREC_COOC_TILE 8192
+int qrec_cooc_workspace_bytes(int64_t n_items, int64_t *bytes);
+int qrec_cooc_count(const int64_t *d_i_indptr, const int32_t *d_i_users, int64_t n_items, int64_t i_nnz, const int64_t *d_u_indptr,
+                    const int32_t *d_u_items, int64_t n_users, int64_t u_nnz, int32_t filter, int64_t *kept, void *d_ws,
+                    int64_t ws_bytes, void *stream);
+int qrec_cooc_fill(const int64_t *d_i_indptr, const int32_t *d_i_users, int64_t n_items, int64_t i_nnz, const int64_t *d_u_indptr,
+                   const int32_t *d_u_items, int64_t n_users, int64_t u_nnz, int32_t filter, int64_t *d_out_indptr,
+                   int32_t *d_out_cols, int32_t *d_out_counts, int64_t capacity, void *d_ws, int64_t ws_bytes, void *stream);
+int qrec_cofactor_item_workspace_bytes(int64_t n_items, int64_t n_ctx_items, int32_t ld, int64_t *bytes);
+int qrec_cofactor_item_rows(const double *d_X, int64_t n_users, const double *d_XtX, double *d_Y, double *d_G, double *d_w, double *d_c,
+                            int64_t n_items, int32_t d, int32_t ld, const int64_t *d_r_indptr, const int32_t *d_r_users,
+                            const double *d_r_conf, int64_t r_nnz, const int64_t *d_s_indptr, const int32_t *d_s_items,
+                            const double *d_s_vals, int64_t s_nnz, const int32_t *d_order, const int32_t *h_level_ptr,
+                            int32_t n_levels, const int32_t *d_solo, int64_t n_solo, double lambda, double gamma, void *d_ws,
+                            int64_t ws_bytes, void *stream);
+
 /* ---- exposure-weighted ALS, fp64 (model/ranking/ExpoMF.py, model/ranking/SERec.py; exposure.hip) --------------------- *
  * Tables as for ALS: fp64 [rows][ld], ld in {16, 32, 64, 128}, 1 <= d <= ld, pad columns zero; d > QREC_ALS_MAX_D returns
  * QREC_ERR_UNSUPPORTED.  The exposure posterior of (row r, column c), from the row's table X and the column's table F:

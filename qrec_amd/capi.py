@@ -154,6 +154,12 @@ _SIGNATURES = {
     "qrec_als_gram": [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp],
     "qrec_als_solve_workspace_bytes": [_vp, _i64, _i32, _vp],
     "qrec_als_solve_rows": [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _f64, _vp, _vp, _i64, _vp],
+    "qrec_cooc_workspace_bytes": [_i64, _vp],
+    "qrec_cooc_count": [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp],
+    "qrec_cooc_fill": [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp],
+    "qrec_cofactor_item_workspace_bytes": [_i64, _i64, _i32, _vp],
+    "qrec_cofactor_item_rows": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp,
+                                _i32, _vp, _i64, _f64, _f64, _vp, _i64, _vp],
     "qrec_expo_solve_workspace_bytes": [_i64, _i32, _vp],
     "qrec_expo_solve_rows": [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _f64, _vp, _i64, _vp],
     "qrec_expo_prior_workspace_bytes": [_i64, _i64, _vp],
@@ -1251,6 +1257,52 @@ def als_solve_rows(d_F, f_rows: int, d_G, d_X, n_rows: int, d: int, ld: int, d_i
     ERR_NOT_SPD when a system is not positive definite (X untouched)."""
     _check(load().qrec_als_solve_rows(_dp(d_F), f_rows, _dp(d_G), _dp(d_X), n_rows, d, ld, _dp(d_indptr), _dp(d_indices), _dp(d_c),
                                       lam, _dp(d_loss), _dp(d_ws), ws_bytes, _sh(stream)))
+
+
+# ---- CoFactor (cofactor.hip) ------------------------------------------------------------------------------------------------
+COOC_TILE = 8192
+
+
+def cooc_workspace_bytes(n_items: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_cooc_workspace_bytes(n_items, C.byref(out)))
+    return out.value
+
+
+def cooc_count(d_i_indptr, d_i_users, n_items: int, i_nnz: int, d_u_indptr, d_u_items, n_users: int, u_nnz: int, filt: int, d_ws,
+               ws_bytes: int, stream=None) -> int:
+    """the number of kept directed pairs (count > filt, both items with >= filt raters); waits for the stream"""
+    kept = C.c_int64(0)
+    _check(load().qrec_cooc_count(_dp(d_i_indptr), _dp(d_i_users), n_items, i_nnz, _dp(d_u_indptr), _dp(d_u_items), n_users, u_nnz, filt,
+                                  C.byref(kept), _dp(d_ws), ws_bytes, _sh(stream)))
+    return kept.value
+
+
+def cooc_fill(d_i_indptr, d_i_users, n_items: int, i_nnz: int, d_u_indptr, d_u_items, n_users: int, u_nnz: int, filt: int, d_out_indptr,
+              d_out_cols, d_out_counts, capacity: int, d_ws, ws_bytes: int, stream=None):
+    """the kept pairs as a CSR with ascending columns, after cooc_count of the same inputs and workspace"""
+    _check(load().qrec_cooc_fill(_dp(d_i_indptr), _dp(d_i_users), n_items, i_nnz, _dp(d_u_indptr), _dp(d_u_items), n_users, u_nnz, filt,
+                                 _dp(d_out_indptr), _dp(d_out_cols), _dp(d_out_counts), capacity, _dp(d_ws), ws_bytes, _sh(stream)))
+
+
+def cofactor_item_workspace_bytes(n_items: int, n_ctx_items: int, ld: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_cofactor_item_workspace_bytes(n_items, n_ctx_items, ld, C.byref(out)))
+    return out.value
+
+
+def cofactor_item_rows(d_X, n_users: int, d_XtX, d_Y, d_G, d_w, d_c, n_items: int, d: int, ld: int, d_r_indptr, d_r_users, d_r_conf,
+                       r_nnz: int, d_s_indptr, d_s_items, d_s_vals, s_nnz: int, d_order, level_ptr, d_solo, n_solo: int, lam: float,
+                       gamma: float, d_ws, ws_bytes: int, stream=None):
+    """CoFactor's item half: the scheduled items level by level (``level_ptr``: host int32), the others as ALS rows; waits
+    for the stream.  QRecError with code ERR_NOT_SPD when a system is not positive definite (tables untouched)."""
+    if level_ptr is not None:
+        _req(level_ptr, np.int32, "level_ptr")
+    n_levels = 0 if level_ptr is None else level_ptr.size - 1
+    _check(load().qrec_cofactor_item_rows(_dp(d_X), n_users, _dp(d_XtX), _dp(d_Y), _dp(d_G), _dp(d_w), _dp(d_c), n_items, d, ld,
+                                          _dp(d_r_indptr), _dp(d_r_users), _dp(d_r_conf), r_nnz, _dp(d_s_indptr), _dp(d_s_items),
+                                          _dp(d_s_vals), s_nnz, _dp(d_order), None if level_ptr is None else _hp(level_ptr), n_levels,
+                                          _dp(d_solo), n_solo, lam, gamma, _dp(d_ws), ws_bytes, _sh(stream)))
 
 
 # ---- exposure-weighted ALS (exposure.hip) ---------------------------------------------------------------------------------

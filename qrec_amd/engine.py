@@ -1057,3 +1057,159 @@ class SlopeOneSolver:
         dev = raw[:nq * self.n_items * 8].view(np.float64).reshape(nq, self.n_items)
         freq = raw[nq * self.n_items * 8: nq * self.n_items * 12].view(np.int32).reshape(nq, self.n_items)
         return dev.copy(), freq.copy()
+
+
+# ---- CoFactor (cofactor.hip) ------------------------------------------------------------------------------------------------
+def sppmi_from_counts(indptr: np.ndarray, cols: np.ndarray, counts: np.ndarray, neg: int):
+    """The SPPMI matrix of model/ranking/CoFactor.py:58-81 from the kept co-occurrence counts (CSR by item id, columns
+    ascending): ``(ptr, idx, val)``, row i = the dict ``SPPMI[i]`` in its insertion order -- the order in which the item step
+    adds its context terms.  Host code, O(nnz log nnz).
+
+    The reference walks ``occurrence`` in the order its keys were first touched: item x at its own turn of the pair loop,
+    or earlier, as the partner of its smallest kept neighbour a < x (during a's turn, after a itself and in ascending x).
+    Walking item a in that order it visits a's partners b in ascending id and inserts b into SPPMI[a] and a into SPPMI[b]
+    when the value is positive; the second visit of a pair finds both present.  So row x holds first the partners walked
+    before x (in walk order), then the others in ascending id.  Values: ``max(log(count * D / (f_a * f_b)) - log(neg), 0)``
+    with the C library's log (math.log, as the reference calls it), divided once by the largest."""
+    import math
+    n = indptr.size - 1
+    deg = np.diff(indptr)
+    rows = np.repeat(np.arange(n, dtype=np.int64), deg)
+    cols = np.asarray(cols, dtype=np.int64)
+    freq = np.bincount(rows, weights=np.asarray(counts, dtype=np.float64), minlength=n)      # integer-valued sums: exact
+    D = float(freq.sum())
+    empty = (np.zeros(n + 1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64))
+    if cols.size == 0:
+        return empty
+    upper = rows < cols
+    arg = (np.asarray(counts, dtype=np.float64)[upper] * D) / (freq[rows[upper]] * freq[cols[upper]])
+    log_neg = math.log(neg)
+    pmi = np.fromiter((math.log(x) - log_neg for x in arg.tolist()), dtype=np.float64, count=arg.size)
+    keep = pmi > 0
+    if not keep.any():
+        return empty
+    a, b, v = rows[upper][keep], cols[upper][keep], pmi[keep] / pmi[keep].max()
+    # the walk order of ``occurrence``'s keys, from the full counts
+    has = np.flatnonzero(deg > 0)
+    first = cols[indptr[has]]
+    early = first < has
+    walk = has[np.lexsort((np.where(early, has, -1), np.where(early, first, has)))]
+    rank = np.full(n, n, dtype=np.int64)
+    rank[walk] = np.arange(walk.size)
+    x, y, val = np.concatenate([a, b]), np.concatenate([b, a]), np.concatenate([v, v])
+    before = rank[y] < rank[x]
+    order = np.lexsort((np.where(before, rank[y], y), ~before, x))
+    ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(x, minlength=n), out=ptr[1:])
+    return ptr, np.ascontiguousarray(y[order], dtype=np.int32), np.ascontiguousarray(val[order])
+
+
+class CoOccurrence:
+    """Item-item co-occurrence of CoFactor (model/ranking/CoFactor.py:36-56) on the device and its SPPMI matrix.
+
+    ``uid`` / ``iid``: the training pairs (duplicates count once).  ``counts()`` runs the two passes of cofactor.hip -- count
+    the kept pairs (count > filt between items with >= filt raters), then fill a CSR allocated for exactly that many
+    (``capacity``: refuse, with nothing written, when there are more) -- and ``sppmi(neg)`` finishes on the host
+    (:func:`sppmi_from_counts`).  ``timings`` holds the milliseconds of the count / fill / host parts of the last run."""
+
+    def __init__(self, uid: np.ndarray, iid: np.ndarray, n_users: int, n_items: int, filt: int, capacity: int | None = None):
+        key = np.unique(np.asarray(uid, dtype=np.int64) * n_items + np.asarray(iid, dtype=np.int64))
+        u, i = key // n_items, key % n_items
+        self.n_users, self.n_items, self.filt, self.capacity, self.nnz = int(n_users), int(n_items), int(filt), capacity, int(key.size)
+        u_indptr, u_items = _csr_by(u, i, n_users)
+        i_indptr, i_users = _csr_by(i, u, n_items)
+        self.d_u_indptr, self.d_u_items = _dev(u_indptr, np.int64), _dev(u_items, np.int32)
+        self.d_i_indptr, self.d_i_users = _dev(i_indptr, np.int64), _dev(i_users, np.int32)
+        self.ws_bytes = capi.cooc_workspace_bytes(n_items)
+        self.d_ws = DeviceBuffer((self.ws_bytes,), np.uint8)
+        self.timings = {}
+
+    def counts(self, stream=None):
+        """(indptr int64 [n_items + 1], cols int32, counts int32) of the kept pairs, columns ascending"""
+        from time import perf_counter
+        views = (self.d_i_indptr, self.d_i_users, self.n_items, self.nnz, self.d_u_indptr, self.d_u_items, self.n_users, self.nnz, self.filt)
+        t0 = perf_counter()
+        kept = capi.cooc_count(*views, self.d_ws, self.ws_bytes, stream)
+        t1 = perf_counter()
+        cap = kept if self.capacity is None else int(self.capacity)
+        d_indptr = DeviceBuffer((self.n_items + 1,), np.int64)
+        d_cols, d_counts = DeviceBuffer((max(cap, 1),), np.int32), DeviceBuffer((max(cap, 1),), np.int32)
+        t2 = perf_counter()
+        capi.cooc_fill(*views, d_indptr, d_cols, d_counts, cap, self.d_ws, self.ws_bytes, stream)
+        t3 = perf_counter()
+        self.kept = kept
+        self.timings.update(count_ms=(t1 - t0) * 1e3, fill_ms=(t3 - t2) * 1e3)
+        return d_indptr.numpy(stream), d_cols.head(kept, stream), d_counts.head(kept, stream)
+
+    def sppmi(self, neg: int, stream=None):
+        from time import perf_counter
+        indptr, cols, counts = self.counts(stream)
+        t0 = perf_counter()
+        out = sppmi_from_counts(indptr, cols, counts, neg)
+        self.timings["host_ms"] = (perf_counter() - t0) * 1e3
+        return out
+
+
+def cofactor_schedule(ptr: np.ndarray, idx: np.ndarray):
+    """The level schedule of CoFactor's item sweep: step k is the k-th item with contexts (ascending id = ``data.item``
+    order); it reads the rows of its contexts and writes its own, so level(i) = 1 + max level(earlier context).
+    Returns (order: item ids level by level, level_ptr)."""
+    from .social import level_schedule
+    n = ptr.size - 1
+    ctx = np.flatnonzero(np.diff(ptr) > 0)
+    read_ptr = np.zeros(ctx.size + 1, dtype=np.int64)
+    np.cumsum(np.diff(ptr)[ctx], out=read_ptr[1:])
+    sched = level_schedule(n, read_ptr, idx, np.arange(ctx.size + 1, dtype=np.int64), ctx)
+    return np.ascontiguousarray(ctx[sched.order], dtype=np.int32), np.ascontiguousarray(sched.level_ptr, dtype=np.int32)
+
+
+class CoFactorSolver:
+    """CoFactor's training (model/ranking/CoFactor.py:84-162) with every table resident in fp64: X, Y (an ``AlsSolver``:
+    the user half is WRMF's), the context embeddings G and the biases w, c, the SPPMI CSR in the reference's neighbour
+    order and the level schedule of the item sweep.  ``epoch()`` = Y^T Y, the user half with the loss, X^T X, the item
+    half (cofactor.hip); it returns the loss.  Every sum has a fixed order: two runs are bit-identical."""
+
+    def __init__(self, X, Y, G, w, c, uid, iid, rating, sppmi, lam: float, gamma: float, alpha: float = 10.0):
+        self.als = AlsSolver(X, Y, uid, iid, rating, lam, alpha)
+        t = self.als.t
+        self.d, self.ld, self.lam, self.gamma = t.d, t.ld, float(lam), float(gamma)
+        self.n_users, self.n_items = t.n_users, t.n_items
+        self.d_Gt = DeviceBuffer.from_numpy(t._pad(np.asarray(G, dtype=np.float64)))
+        self.d_w, self.d_c = _dev(w, np.float64), _dev(c, np.float64)
+        ptr, idx, val = sppmi
+        assert ptr.size == self.n_items + 1
+        self.s_nnz = int(idx.size)
+        self.d_s_ptr, self.d_s_idx, self.d_s_val = _dev(ptr, np.int64), _dev(idx, np.int32), _dev(val, np.float64)
+        order, self.level_ptr = cofactor_schedule(ptr, idx)
+        solo = np.flatnonzero(np.diff(ptr) == 0)
+        self.n_ctx, self.n_solo = int(order.size), int(solo.size)
+        self.d_order, self.d_solo = _dev(order, np.int32), _dev(solo, np.int32)
+        widths = np.diff(self.level_ptr)
+        self.schedule = dict(depth=int(widths.size), max_width=int(widths.max()) if widths.size else 0, items=self.n_ctx,
+                             entries=self.s_nnz, longest_row=int(np.diff(ptr).max()) if self.n_items else 0)
+        self.item_ws_bytes = capi.cofactor_item_workspace_bytes(self.n_items, self.n_ctx, self.ld)
+        self.d_item_ws = DeviceBuffer((self.item_ws_bytes,), np.uint8)
+        self.timings = {}
+
+    def item_half(self, stream=None):
+        a, h = self.als, self.als.halves[1]
+        capi.als_gram(a.t.P, self.n_users, self.d, self.ld, a.d_G, a.d_gram_ws, a.gram_ws_bytes, stream)
+        capi.cofactor_item_rows(a.t.P, self.n_users, a.d_G, a.t.Q, self.d_Gt, self.d_w, self.d_c, self.n_items, self.d, self.ld,
+                                h["d_indptr"], h["d_indices"], h["d_c"], int(h["indptr"][-1]), self.d_s_ptr, self.d_s_idx, self.d_s_val,
+                                self.s_nnz, self.d_order, self.level_ptr, self.d_solo, self.n_solo, self.lam, self.gamma,
+                                self.d_item_ws, self.item_ws_bytes, stream)
+
+    def epoch(self, stream=None) -> float:
+        from time import perf_counter
+        t0 = perf_counter()
+        self.als.half(0, True, stream)
+        loss = float(self.als.d_loss.numpy(stream)[0])
+        t1 = perf_counter()
+        self.item_half(stream)
+        self.timings.update(user_half_ms=(t1 - t0) * 1e3, item_half_ms=(perf_counter() - t1) * 1e3)
+        return loss
+
+    def download(self):
+        """(X, Y, G, w, c) as fp64 host arrays"""
+        X, Y = self.als.download()
+        return X, Y, np.ascontiguousarray(self.d_Gt.numpy()[:, :self.d]), self.d_w.head(self.n_items), self.d_c.head(self.n_items)
