@@ -176,3 +176,23 @@ def test_round4_entry_points_refuse_bad_arguments_and_treat_empty_inputs_as_no_o
     assert not ones.numpy().any()
     capi.batch_rows_scatter_add(T, 64, 5000, 5100, idx, idx, idx, 16, 50, DB.from_numpy(np.ones((48, 64), np.float32)))
     assert np.array_equal(T.numpy(), before)
+
+
+def test_gather_pairs_refuses_bad_arguments_gathers_by_the_permutation_and_treats_n_0_as_a_no_op():
+    """qrec_gather_pairs: (u_out, i_out)[t] = (u, i)[perm[t]] for t < n, nothing beyond n, nothing at all for n = 0"""
+    u, i = np.arange(10, 20, dtype=np.int32), np.arange(100, 110, dtype=np.int32)
+    perm = np.array([3, 0, 9, 9, 1], dtype=np.int32)
+    d_u, d_i, d_p = DB.from_numpy(u), DB.from_numpy(i), DB.from_numpy(perm)
+    before = np.full(8, -7, np.int32)
+    ou, oi = DB.from_numpy(before), DB.from_numpy(before)
+    assert "null" in _err(lambda: capi.gather_pairs(d_p, d_u, None, 5, ou, oi))
+    assert "null" in _err(lambda: capi.gather_pairs(None, d_u, d_i, 5, ou, oi))
+    assert "null" in _err(lambda: capi.gather_pairs(d_p, d_u, d_i, 5, ou, None))
+    assert "negative" in _err(lambda: capi.gather_pairs(d_p, d_u, d_i, -1, ou, oi))
+    capi.gather_pairs(d_p, d_u, d_i, 0, ou, oi); capi.gather_pairs(None, None, None, 0, None, None)     # n = 0: nothing is dereferenced
+    capi.device_sync()
+    assert np.array_equal(ou.numpy(), before) and np.array_equal(oi.numpy(), before)
+    s = capi.Stream()
+    capi.gather_pairs(d_p, d_u, d_i, 5, ou, oi, s); s.sync()
+    assert np.array_equal(ou.numpy(), np.concatenate([u[perm], before[5:]])) and np.array_equal(oi.numpy(), np.concatenate([i[perm], before[5:]]))
+    assert np.array_equal(d_u.numpy(), u) and np.array_equal(d_i.numpy(), i) and np.array_equal(d_p.numpy(), perm)

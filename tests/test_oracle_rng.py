@@ -124,3 +124,78 @@ def test_philox_sampler_contract_against_a_python_loop():
                     want = cand[0]; break
             assert j[t] == want, (n_items, t, u, j[t], want)
         assert (j[row_user == 3] == -1).all() and (j[row_user != 3] >= 0).all()
+
+
+# ---- the throughput mode's device stream: its distribution ---------------------------------------------------------------------
+# The GPU tests pin the device to the oracle bit for bit (test_philox_sampler_stream_equals_the_oracle, test_device_permutation_stream_
+# equals_the_oracle, test_device_batch_stream_equals_the_oracle_under_asynchronous_readers), so what the stream is DISTRIBUTED like can be
+# tested here, without a GPU and with fixed seeds: pass or fail forever.  Threshold of every chi-square: the 1 - 1e-6 quantile.
+def _chi2_threshold(dof: int) -> float:
+    try:
+        from scipy.stats import chi2
+        return float(chi2.isf(1e-6, dof))
+    except ImportError:                                                   # Wilson-Hilferty; z = the normal's 1 - 1e-6 quantile
+        z = 4.753424308822899
+        return dof * (1 - 2 / (9 * dof) + z * (2 / (9 * dof)) ** 0.5) ** 3
+
+
+def _chi2(counts, expected) -> float:
+    counts = np.asarray(counts, dtype=np.float64); expected = np.broadcast_to(np.asarray(expected, dtype=np.float64), counts.shape)
+    return float(((counts - expected) ** 2 / expected).sum())
+
+
+STREAM_EPOCHS = (0, 1, 2 ** 33 + 1, 7)
+
+
+@pytest.mark.parametrize("n_items,n_rated,seed", [(64, 40, 2 ** 40 + 17), (65, 1, 99)])
+def test_philox_negatives_are_uniform_over_the_unrated_items(n_items, n_rated, seed):
+    """one user, repeated 300,000 times as row_user over four epochs (one >= 2^32): 1.2 M draws, never a rated item, counts over the
+    unrated ones uniform.  Item counts at and next to a power of two: the candidate is a (bit_length)-bit word, rejected when >= n_items."""
+    rated = np.sort(np.random.default_rng(n_items).choice(n_items, size=n_rated, replace=False)).astype(np.int32)
+    # a second user in front, so that the row of the user under test does not start at 0
+    indptr = np.array([0, 3, 3 + n_rated], dtype=np.int64)
+    items = np.concatenate([np.array([0, 1, 2], np.int32), rated])
+    row_user = np.ones(300_000, dtype=np.int32)
+    counts = np.zeros(n_items, dtype=np.int64)
+    for epoch in STREAM_EPOCHS:
+        j = O.philox_bpr_sample(indptr, items, row_user, n_items, seed, epoch)
+        assert ((j >= 0) & (j < n_items)).all()
+        counts += np.bincount(j, minlength=n_items)
+    assert counts[rated].sum() == 0, "a rated item was drawn"
+    unrated = np.setdiff1d(np.arange(n_items), rated)
+    total = row_user.size * len(STREAM_EPOCHS)
+    assert counts[unrated].sum() == total
+    x2, bound = _chi2(counts[unrated], total / unrated.size), _chi2_threshold(unrated.size - 1)
+    assert x2 < bound, f"negatives over {unrated.size} unrated of {n_items} items: chi-square {x2:.1f}, threshold {bound:.1f} ({unrated.size - 1} dof)"
+    # two epochs are two streams, and two seeds likewise
+    a, b = O.philox_bpr_sample(indptr, items, row_user, n_items, seed, 2 ** 33 + 1), O.philox_bpr_sample(indptr, items, row_user, n_items, seed, 1)
+    assert not np.array_equal(a, b)                                       # the high word of the epoch is not dropped
+    assert not np.array_equal(a, O.philox_bpr_sample(indptr, items, row_user, n_items, seed + 2 ** 32, 2 ** 33 + 1))
+
+
+def test_philox_shuffle_is_uniform_in_position_batch_and_adjacency():
+    """n = 1000 rows, 20,000 stream ids from 2^32 on (seed >= 2^32 too): where row 0 lands (1000 cells), which batch of 64 holds row 999
+    (16 batches, the last one 40 rows), and how often row 1 directly follows row 0 (probability 1 / n)."""
+    n, seed, S, batch = 1000, 2 ** 40 + 3, 20_000, 64
+    pos0 = np.zeros(n, dtype=np.int64)
+    n_batches = -(-n // batch)
+    in_batch = np.zeros(n_batches, dtype=np.int64)
+    follows = 0
+    for sid in range(2 ** 32, 2 ** 32 + S):
+        perm = O.philox_permutation(n, seed, sid)
+        inv = np.empty(n, dtype=np.int64); inv[perm] = np.arange(n)
+        pos0[inv[0]] += 1
+        in_batch[inv[999] // batch] += 1
+        follows += int(inv[1] == inv[0] + 1)
+    assert pos0.sum() == S and in_batch.sum() == S
+    x2, bound = _chi2(pos0, S / n), _chi2_threshold(n - 1)
+    assert x2 < bound, f"position of row 0: chi-square {x2:.1f}, threshold {bound:.1f} ({n - 1} dof)"
+    rows_in_batch = np.minimum(batch, n - batch * np.arange(n_batches))
+    assert rows_in_batch[-1] == 40
+    x2, bound = _chi2(in_batch, S * rows_in_batch / n), _chi2_threshold(n_batches - 1)
+    assert x2 < bound, f"batch holding row 999: chi-square {x2:.1f}, threshold {bound:.1f} ({n_batches - 1} dof)"
+    mean, sigma = S / n, (S * (1 / n) * (1 - 1 / n)) ** 0.5
+    assert abs(follows - mean) < 5 * sigma, f"row 1 directly after row 0 in {follows} of {S} epochs, expected {mean:.0f} +- 5 x {sigma:.1f}"
+    # stream ids that differ in the high word only are different shuffles
+    assert not np.array_equal(O.philox_permutation(n, seed, 3), O.philox_permutation(n, seed, 2 ** 32 + 3))
+    assert not np.array_equal(O.philox_permutation(n, seed, 3), O.philox_permutation(n, seed - 2 ** 40, 3))
