@@ -444,6 +444,35 @@ int qrec_copy_cols(float *d_dst, int32_t dst_ld, const float *d_src, int32_t src
 /* X[row][0 .. ld) = 0 for the listed rows (a row subset as above): clears a gradient table where the next scatter lands */
 int qrec_zero_rows(float *d_X, int32_t ld, const int32_t *d_row_ids, const int32_t *d_n_row_ids, int32_t max_row_ids, void *stream);
 
+/* ---- the dense layer of DiffNet / DHCF (model/ranking/DiffNet.py:46-49, DHCF.py:74-87; csrc/dense_layer.hip) ---- *
+ * Tables [n_rows][ld] fp32, ld in {32, 64, 128} (anything else is refused).  d_W holds one zero-padded [ld][ld] block per
+ * operand: block 0 multiplies X1, block 1 multiplies X2 (a (2d x d) weight = its two d x d halves).  No float atomics:
+ * the same inputs give the same bits on every launch.                                                          */
+
+/* Y = [X1 | X2] W (+ R), through ReLU when relu != 0.  d_X2 and d_R may be NULL. */
+int qrec_dense_layer_fwd(const float *d_X1, const float *d_X2, const float *d_W, const float *d_R, int64_t n_rows, int32_t ld,
+                         int32_t relu, float *d_Y, void *stream);
+/* ReluGrad: dpre = dY where Y > 0, else 0 */
+int qrec_dense_layer_dpre_relu(const float *d_dY, const float *d_Y, int64_t n_rows, int32_t ld, float *d_dpre, void *stream);
+/* Backward of qrec_ngcf_activate when the NORMALISED rows are what the next layer carries on (DHCF.py:78-90):
+ * dz = block [col_off, col_off + d) of d_dWide + d_dZ_next (may be NULL); dpre = (dz - z (z.dz)) * inv_norm * gate. */
+int qrec_dense_layer_dpre_norm(const float *d_dWide, const float *d_wide, int32_t wide_ld, int32_t col_off, const float *d_dZ_next,
+                               const float *d_inv_norm, const float *d_gate, int64_t n_rows, int32_t d, int32_t ld, float *d_dpre,
+                               void *stream);
+/* dX1 (+= when accumulate_dX1, else =) dpre W[0]^T; dX2 = dpre W[1]^T; gW[w] = X_w^T dpre (per-slab partial products in
+ * d_ws, added in slab order).  The residual's gradient is dpre itself.  d_X2 / d_dX2 both NULL or both given.
+ * d_ws: at least qrec_dense_layer_ws_bytes(n_rows, ld, n_w) bytes, n_w = 1 or 2 operands; a smaller one is refused. */
+int qrec_dense_layer_bwd(const float *d_dpre, const float *d_X1, const float *d_X2, const float *d_W, int64_t n_rows, int32_t ld,
+                         int32_t accumulate_dX1, float *d_dX1, float *d_dX2, float *d_gW, void *d_ws, int64_t ws_bytes,
+                         void *stream);
+int qrec_dense_layer_ws_bytes(int64_t n_rows, int32_t ld, int32_t n_w, int64_t *bytes);
+/* The loss of qrec_bpr_batch_loss_grad (same rows, same per-triplet arithmetic) in a FIXED order, for parity runs: that call adds
+ * its blocks' sums with fp64 atomics, whose order -- and with it the last bits of the loss -- changes from launch to launch.
+ * Block k of n_slots walks its triplets in order and ASSIGNS its sum to d_slots[k]; the loss is the slots added in order
+ * (host).  No gradient is formed here. */
+int qrec_bpr_batch_loss_slots(const float *d_S, float div, int32_t n_users, int32_t ld, const int32_t *d_u, const int32_t *d_i,
+                              const int32_t *d_j, int32_t B, float eps, float reg, double *d_slots, int32_t n_slots, void *stream);
+
 /* ---- per-epoch graph augmentation on the device (SGL.py:113-155, BUIR.py:41-65; throughput mode) ----------------------------
  * A sub-graph of the training graph as a VALUE array over the full graph's CSR structure (csrc/augment.hip): entry e of the joint
  * adjacency gets fl32(fl32(d'_r a'_e) d'_c) with a'_e = the number of kept training rows that map to it and d' = deg'^-1/2 of the

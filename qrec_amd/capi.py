@@ -106,6 +106,12 @@ _SIGNATURES = {
     "qrec_ngcf_activate": [_vp, _i64, _i32, _i32, _f32, _vp, _u64, _u64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i64, _vp],
     "qrec_ngcf_layer_bwd": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
     "qrec_ngcf_wgrad_partial_bytes": [_i64, _i32, _vp],
+    "qrec_dense_layer_fwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp],
+    "qrec_dense_layer_dpre_relu": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "qrec_dense_layer_dpre_norm": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp],
+    "qrec_dense_layer_bwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
+    "qrec_dense_layer_ws_bytes": [_i64, _i32, _i32, _vp],
+    "qrec_bpr_batch_loss_slots": [_vp, _f32, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _i32, _vp],
     "qrec_copy_cols": [_vp, _i32, _vp, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _i32, _vp],
     "qrec_zero_rows": [_vp, _i32, _vp, _vp, _i32, _vp],
     "qrec_score_topk_scratch_bytes": [C.c_int, _i32, _i32, _i32, _i32, _vp],
@@ -1030,6 +1036,39 @@ def copy_cols(d_dst, dst_ld: int, d_src, src_ld: int, src_col_off: int, n_rows: 
               stream=None, rows=None):
     _check(load().qrec_copy_cols(_dp(d_dst), dst_ld, _dp(d_src), src_ld, src_col_off, n_rows, d, 1 if accumulate else 0,
                                  *_subset(rows), _sh(stream)))
+
+
+def dense_layer_fwd(d_X1, d_X2, d_W, d_R, n_rows: int, ld: int, relu: bool, d_Y, stream=None):
+    """Y = [X1 | X2] W (+ R), optionally through ReLU; d_X2 / d_R may be None (include/qrec_hip.h, csrc/dense_layer.hip)"""
+    _check(load().qrec_dense_layer_fwd(_dp(d_X1), _dp(d_X2), _dp(d_W), _dp(d_R), n_rows, ld, 1 if relu else 0, _dp(d_Y), _sh(stream)))
+
+
+def dense_layer_dpre_relu(d_dY, d_Y, n_rows: int, ld: int, d_dpre, stream=None):
+    _check(load().qrec_dense_layer_dpre_relu(_dp(d_dY), _dp(d_Y), n_rows, ld, _dp(d_dpre), _sh(stream)))
+
+
+def dense_layer_dpre_norm(d_dWide, d_wide, wide_ld: int, col_off: int, d_dZ_next, d_inv_norm, d_gate, n_rows: int, d: int, ld: int,
+                          d_dpre, stream=None):
+    _check(load().qrec_dense_layer_dpre_norm(_dp(d_dWide), _dp(d_wide), wide_ld, col_off, _dp(d_dZ_next), _dp(d_inv_norm), _dp(d_gate),
+                                             n_rows, d, ld, _dp(d_dpre), _sh(stream)))
+
+
+def dense_layer_ws_bytes(n_rows: int, ld: int, n_w: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_dense_layer_ws_bytes(n_rows, ld, n_w, C.byref(out)))
+    return out.value
+
+
+def dense_layer_bwd(d_dpre, d_X1, d_X2, d_W, n_rows: int, ld: int, d_dX1, d_dX2, d_gW, d_ws, accumulate_dX1: bool = False, stream=None):
+    """dX1 (=|+=) dpre W[0]^T, dX2 = dpre W[1]^T, gW = [X1 | X2]^T dpre; d_ws: a DeviceBuffer of dense_layer_ws_bytes bytes"""
+    _check(load().qrec_dense_layer_bwd(_dp(d_dpre), _dp(d_X1), _dp(d_X2), _dp(d_W), n_rows, ld, 1 if accumulate_dX1 else 0, _dp(d_dX1),
+                                       _dp(d_dX2), _dp(d_gW), _dp(d_ws), d_ws.nbytes, _sh(stream)))
+
+
+def bpr_batch_loss_slots(d_S, div: float, n_users: int, ld: int, d_u, d_i, d_j, B: int, eps: float, reg: float, d_slots, stream=None):
+    """the batch loss of bpr_batch_loss_grad in a fixed order: one partial sum per element of d_slots (float64), to be added in order"""
+    _check(load().qrec_bpr_batch_loss_slots(_dp(d_S), div, n_users, ld, _dp(d_u), _dp(d_i), _dp(d_j), B, eps, reg, _dp(d_slots),
+                                            int(np.prod(d_slots.shape)), _sh(stream)))
 
 
 def zero_rows(d_X, ld: int, rows: RowSubset, stream=None):

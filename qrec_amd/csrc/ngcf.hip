@@ -14,13 +14,11 @@
 // Tables are [rows][ld] fp32 with ld in {32, 64, 128}; the d x d weights are stored zero-padded as
 // [ld][ld].  The N x d x d products are the only GEMM-shaped work (2 N d^2 FLOP each, K = d small):
 // one wavefront per 32 rows holds its A fragments in registers and sweeps the output column tiles.
-#include "common.h"
+#include "mfma_rows.h"
 
 using namespace qrec;
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ void philox10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -33,9 +31,6 @@ __device__ __forceinline__ void philox10(uint32_t (&c)[4], uint32_t k0, uint32_t
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
 }
-
-// C/D layout of v_mfma_f32_32x32x2_f32: col = lane&31, row = (q&3) + 8*(q>>2) + 4*(lane>>5)
-__device__ __forceinline__ int cd_row(int q, int h) { return (q & 3) + 8 * (q >> 2) + 4 * h; }
 
 // pre[32 rows][ld] = (side + E) W1 + (E*side) W2      NT = ld/32 output column tiles
 // Persistent blocks: the two weight matrices are staged in LDS once per block (2 x LD*LD floats) and every
@@ -287,43 +282,7 @@ __global__ __launch_bounds__(256) void dense_bwd_kernel(const float *__restrict_
 // tiles and 131 have a third: 21.4 us, of which 5 are that ragged third round.  Two wavefronts per SIMD without the
 // prefetch: 24.6 us.
 // =============================================================================================
-constexpr int kTilePad = 4;
-
-template <int LD>
-struct RowTile {                                  // a wavefront's view of one 32 x LD tile
-    static constexpr int RS = LD + kTilePad;      // LDS row stride (floats)
-    static constexpr int LPRW = LD / 4;           // lanes per row in the load layout
-    static constexpr int RPI = kWave / LPRW;      // rows per load instruction
-    static constexpr int NV = 32 / RPI;           // float4 per lane per tile
-    int lrow, lcol;
-    __device__ explicit RowTile(int lane) : lrow(lane / LPRW), lcol(4 * (lane % LPRW)) {}
-    // row_ids (may be null): the tile's rows are row_ids[row0 ...] instead of row0 ... (a listed subset of the table)
-    __device__ void load(const float *__restrict__ X, int64_t row0, int64_t n_rows, f32x4 (&v)[NV],
-                         const int32_t *__restrict__ row_ids = nullptr) const {
-#pragma unroll
-        for (int k = 0; k < NV; k++) {
-            int64_t row = row0 + k * RPI + lrow;
-            if (row >= n_rows) row = n_rows - 1;                 // rows past the end: a copy of the last row, never stored
-            if (row_ids) row = row_ids[row];
-            v[k] = *reinterpret_cast<const f32x4 *>(X + row * LD + lcol);
-        }
-    }
-    __device__ void park(float *tile, const f32x4 (&v)[NV]) const {
-#pragma unroll
-        for (int k = 0; k < NV; k++) *reinterpret_cast<f32x4 *>(tile + (k * RPI + lrow) * RS + lcol) = v[k];
-    }
-    // MFMA A fragment of lane (r, h): columns [32h, 32h + 32) of row r (LD = 32: the upper k-slot feeds zeros)
-    __device__ static void fragment(const float *tile, int r, int h, float (&a)[32]) {
-        const bool kv = 32 * h < LD;
-        const float keep = kv ? 1.f : 0.f;
-        const float *p = tile + r * RS + (kv ? 32 * h : 0);
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(p + 4 * q);
-            a[4 * q] = v.x * keep; a[4 * q + 1] = v.y * keep; a[4 * q + 2] = v.z * keep; a[4 * q + 3] = v.w * keep;
-        }
-    }
-};
+// (the wavefront tile itself: RowTile, mfma_rows.h)
 
 template <int NT>
 __global__ __launch_bounds__(256) void dense_fwd_lds_kernel(const float *__restrict__ E, const float *__restrict__ side,

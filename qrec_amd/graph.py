@@ -2006,3 +2006,11 @@ class MHCNTrainer:
         out = {k: (b.numpy()[:d, :d].copy() if len(b.shape) == 2 else b.numpy()[None, :d].copy()) for k, b in self.w.items()}
         out["U"], out["V"] = self.U.numpy()[:, :d].copy(), self.V.numpy()[:, :d].copy()
         return out
+
+
+def __getattr__(name):
+    """DiffNetTrainer / DHCFTrainer live in qrec_amd/diffusion.py (which builds on this module) and are reached from here"""
+    if name in ("DiffNetTrainer", "DHCFTrainer"):
+        from . import diffusion
+        return getattr(diffusion, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

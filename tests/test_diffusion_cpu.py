@@ -1,0 +1,133 @@
+"""CPU side of DiffNet / DHCF: the float64 mirror (tests/diffusion_mirror.py) against the reference's own recorded runs, its
+gradients against finite differences, the product's host-side graph builders against the mirror, the class lookup."""
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import diffusion_cases as C
+import diffusion_mirror as M
+from helpers import check, rel_err
+
+
+def _replay(name):
+    """the mirror through the fixture's batches: (losses, first-step gradients, trained variables)"""
+    m, z = C.load(name)
+    nu, ni = m["n_users"], m["n_items"]
+    names = C.VARS[name]
+    opt = M.Adam([z[f"init_{v}"] for v in names], m["lr"])
+    if name == C.DIFFNET:
+        S = M.social_matrix(nu, z["follower"], z["followee"]); A = M.rating_matrix(nu, ni, z["train_uid"], z["train_iid"])
+    else:
+        Au, Ai = M.dhcf_operators(nu, ni, z["train_uid"], z["train_iid"])
+        H = sp.block_diag([Au, Ai]).tocsr()
+    losses, first = [], None
+    for k, u, i, j in C.batches(z):
+        U, V, W = opt.p[0], opt.p[1], opt.p[2:]
+        if name == C.DIFFNET:
+            loss, dU, dV, dW = M.diffnet_loss_grads(U, V, W, S, A, u, i, j, m["regU"])
+        else:
+            loss, dU, dV, dW = M.dhcf_loss_grads(U, V, W, H, u, i, j, m["regU"], masks=C.dhcf_masks(m, z, k))
+        losses.append(loss)
+        if k == 0:
+            first = [dU, dV] + dW
+        opt.step([dU, dV] + dW)
+    return m, z, np.array(losses), first, opt.p
+
+
+@pytest.mark.parametrize("name", [C.DIFFNET, C.DHCF])
+def test_mirror_reproduces_the_reference_run(name):
+    """losses of all steps and first-step gradients at 1e-5; trained variables at max(1e-5, 2.5 floors), the floor being the
+    committed float32 run's distance from the committed float64 run of the same batches and masks"""
+    m, z, losses, first, final = _replay(name)
+    assert losses.size == m["n_steps"] >= 12
+    check(f"{name} losses vs the reference run", rel_err(losses, z["losses"][:, 0]), C.GRAD_TOL)
+    for v, g, p in zip(C.VARS[name], first, final):
+        check(f"{name} first-step gradient of {v}", rel_err(g, z[f"grad0_{v}"]), C.GRAD_TOL)
+        floor = C.floor_of(name, f"final_{v}", z)
+        check(f"{name} floor of {v} (recorded)", floor, 1.0, kind="info")
+        check(f"{name} trained {v} vs the reference run", rel_err(p, z[f"final_{v}"]), C.trained_bound(name, f"final_{v}", z), kind="floor")
+        check(f"{name} trained {v} vs the float64 run", rel_err(p, C.YARD[f"{name}/final_{v}"]), C.trained_bound(name, f"final_{v}", z), kind="floor")
+
+
+def _fd(f, params, grads, rng, n_probe=6, h=1e-6):
+    """central differences of f along random directions of every parameter against <grad, direction>"""
+    worst = 0.0
+    for p, g in zip(params, grads):
+        for _ in range(n_probe):
+            dirn = rng.standard_normal(p.shape)
+            old = p.copy()
+            p[...] = old + h * dirn; fp = f()
+            p[...] = old - h * dirn; fm = f()
+            p[...] = old
+            num, ana = (fp - fm) / (2 * h), float((g * dirn).sum())
+            worst = max(worst, abs(num - ana) / max(abs(ana), 1e-8))
+    return worst
+
+
+def _toy(rng, nu=23, ni=31, d=5, nnz=140, B=40):
+    uid = rng.integers(0, nu, nnz); iid = rng.integers(0, ni, nnz)
+    keep = np.unique(np.stack([uid, iid], 1), axis=0)
+    uid, iid = keep[:, 0], keep[:, 1]
+    b = rng.integers(0, uid.size, B)
+    u, i, j = uid[b], iid[b], rng.integers(0, ni, B)
+    U, V = rng.standard_normal((nu, d)) * 0.3, rng.standard_normal((ni, d)) * 0.3
+    return nu, ni, d, uid, iid, u, i, j, U, V
+
+
+def test_mirror_gradients_match_finite_differences():
+    rng = np.random.default_rng(5)
+    nu, ni, d, uid, iid, u, i, j, U, V = _toy(rng)
+    fo = rng.integers(0, nu, 50); fe = rng.integers(0, nu, 50)
+    S = M.social_matrix(nu, fo, fe); A = M.rating_matrix(nu, ni, uid, iid)
+    for L in (1, 2, 3):
+        Ws = [rng.standard_normal((2 * d, d)) * 0.5 for _ in range(L)]
+        _, dU, dV, dW = M.diffnet_loss_grads(U, V, Ws, S, A, u, i, j, 0.05)
+        worst = _fd(lambda: M.diffnet_loss_grads(U, V, Ws, S, A, u, i, j, 0.05)[0], [U, V] + Ws, [dU, dV] + dW, rng)
+        check(f"DiffNet mirror, {L} layers: analytic vs central differences", worst, 1e-5)
+    Au, Ai = M.dhcf_operators(nu, ni, uid, iid)
+    H = sp.block_diag([Au, Ai]).tocsr()
+    Ws = [rng.standard_normal((d, d)) * 0.5 for _ in range(2)]
+    masks = [(rng.random((nu + ni, d)) >= 0.1).astype(np.float64) for _ in range(2)]
+    for mk in (None, masks):
+        _, dU, dV, dW = M.dhcf_loss_grads(U, V, Ws, H, u, i, j, 0.05, masks=mk)
+        worst = _fd(lambda: M.dhcf_loss_grads(U, V, Ws, H, u, i, j, 0.05, masks=mk)[0], [U, V] + Ws, [dU, dV] + dW, rng)
+        check("DHCF mirror: analytic vs central differences", worst, 1e-5)
+
+
+def test_factored_dhcf_operator_equals_the_formed_product():
+    """diag(A_u, A_i) = P Q on the fixture graph: the product's float32 factors against scipy's formed matrices (DHCF.py:33-47)"""
+    from qrec_amd.diffusion import dhcf_factor_graphs
+    m, z = C.load(C.DHCF)
+    nu, ni = m["n_users"], m["n_items"]
+    Au, Ai = M.dhcf_operators(nu, ni, z["train_uid"], z["train_iid"])
+    H = sp.block_diag([Au, Ai]).tocsr()
+    P, Q = dhcf_factor_graphs(nu, ni, z["train_uid"], z["train_iid"])
+    assert P.dtype == np.float32 and P.nnz == Q.nnz == 2 * np.unique(np.stack([z["train_uid"], z["train_iid"]], 1), axis=0).shape[0]
+    X = np.random.default_rng(0).standard_normal((nu + ni, 8))
+    check("factored operator applied to a table vs the formed one", rel_err(P.astype(np.float64) @ (Q.astype(np.float64) @ X), H @ X), 1e-6)
+    Pm, Qm = M.dhcf_factors(nu, ni, z["train_uid"], z["train_iid"])
+    check("product's factors vs the mirror's", max(rel_err(P.toarray(), Pm.toarray()), rel_err(Q.toarray(), Qm.toarray())), 1e-6)
+    check("formed from the factors vs formed by scipy", rel_err((Pm @ Qm).toarray(), H.toarray()), 1e-12)
+
+
+def test_social_csr_of_the_product_equals_the_mirror():
+    from qrec_amd.diffusion import rating_mean_csr, social_csr
+    m, z = C.load(C.DIFFNET)
+    nu, ni = m["n_users"], m["n_items"]
+    assert z["follower"].size == m["n_relations"] and np.unique(z["follower"]).size == m["users_with_followee"] > 200
+    S, Sm = social_csr(nu, z["follower"], z["followee"]), M.social_matrix(nu, z["follower"], z["followee"])
+    assert S.dtype == np.float32 and np.array_equal(S.toarray().astype(np.float64), Sm.toarray())
+    rows = np.asarray(Sm.sum(1)).ravel()
+    assert np.allclose(rows[np.unique(z["follower"])], 1.0, atol=1e-6) and (rows[np.setdiff1d(np.arange(nu), z["follower"])] == 0).all()
+    A, Am = rating_mean_csr(nu, ni, z["train_uid"], z["train_iid"]), M.rating_matrix(nu, ni, z["train_uid"], z["train_iid"])
+    assert np.array_equal(A.toarray().astype(np.float64), Am.toarray())
+    # a pair listed twice adds up
+    S2 = social_csr(3, np.array([0, 0, 0, 1]), np.array([1, 1, 2, 2]))
+    assert S2.toarray().tolist() == [[0.0, 1.0, 0.5], [0.0, 0.0, 1.0], [0.0, 0.0, 0.0]]
+
+
+@pytest.mark.parametrize("name", ["DiffNet", "DHCF"])
+def test_resolve_model_returns_the_class(name):
+    from qrec_amd.QRec import resolve_model
+    cls = resolve_model(name)
+    assert cls.__name__ == name and hasattr(cls, "trainModel") and hasattr(cls, "predictForRanking")
