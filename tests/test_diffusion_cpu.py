@@ -1,9 +1,11 @@
 """CPU side of DiffNet / DHCF: the float64 mirror (tests/diffusion_mirror.py) against the reference's own recorded runs, its
-gradients against finite differences, the product's host-side graph builders against the mirror, the class lookup."""
+gradients against finite differences, the product's host-side graph builders against the mirror, the class lookup, and the
+headroom under 2^24 on which the bit-for-bit dense-layer cases of tests/test_gpu_dense_layer.py rest."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import dense_layer_cases as D
 import diffusion_cases as C
 import diffusion_mirror as M
 from helpers import check, rel_err
@@ -131,3 +133,57 @@ def test_resolve_model_returns_the_class(name):
     from qrec_amd.QRec import resolve_model
     cls = resolve_model(name)
     assert cls.__name__ == name and hasattr(cls, "trainModel") and hasattr(cls, "predictForRanking")
+
+
+# ---- the integer cases of the dense-layer tests are exact in fp32 ------------------------------------------------------------------
+@pytest.mark.parametrize("ld,d,n", D.EXACT_CASES)
+def test_integer_dense_layer_cases_stay_below_two_to_the_24(ld, d, n):
+    """tests/test_gpu_dense_layer.py asserts array_equal between fp32 MFMA results and the float64 mirror on these inputs.  That
+    holds whatever the summation tree iff no sum of absolute products (+ residual, + prior dX1) reaches 2^24: checked here in
+    float64 for every output of every mode, the 69,669-row weight gradient included."""
+    t = D.integer_inputs(ld, d, n)
+    for a in t.values():
+        assert a.dtype == np.float32 and np.array_equal(a, np.round(a)) and np.abs(a).max() == 2
+    for mode, worst in D.headroom(t).items():
+        check("integer dense-layer case: largest sum of |a||b| over all outputs", worst, D.EXACT_LIMIT, ctx=(ld, d, n, mode), kind="info")
+        assert worst < D.EXACT_LIMIT
+
+
+@pytest.mark.parametrize("ld,d,n", D.NORM_CASES)
+def test_integer_dpre_norm_cases_stay_below_two_to_the_24(ld, d, n):
+    """the same for dpre = (dz - z (z.dz)) inv gate: integers times powers of two, every intermediate far below 2^24"""
+    t = D.norm_integer_inputs(ld, d, n)
+    assert np.abs(t["dAll"]).min() >= 1 and np.abs(t["All"]).min() >= 1 and not t["gate"][:, d:].any() and not t["dZ"][:, d:].any()
+    for col_off in (d, 2 * d):
+        assert D.norm_headroom(t, d, col_off) < D.EXACT_LIMIT
+    # the float64 formula the GPU test compares with, against an independent statement of it on one row
+    want = D.dpre_norm_f64(t["dAll"], t["All"], d, t["dZ"], t["inv"], t["gate"], d)
+    z = t["All"][0, d:2 * d].astype(np.float64); dz = t["dAll"][0, d:2 * d].astype(np.float64) + t["dZ"][0, :d]
+    jac = (np.eye(d) - np.outer(z, z)) * float(t["inv"][0])          # d normalize / d nxt at |nxt| = 1 / inv, z taken as given
+    assert np.array_equal(want[0], (jac @ dz) * t["gate"][0, :d])
+
+
+def test_worst_tile_pins_an_error_the_table_norm_dilutes():
+    want = np.ones((70000, 64)); got = want.copy()
+    got[32 * 7:32 * 8] *= 1 + 1e-4                                     # one wavefront's tile off by 1e-4
+    assert rel_err(got, want) < C.GRAD_TOL < D.worst_tile(got, want)
+    assert abs(D.worst_tile(got, want) - 1e-4) < 1e-9 and D.worst_tile(want, want) == 0.0
+    z = np.zeros((40, 4)); e = z.copy(); e[35, 1] = 1e-30              # a tile whose reference is zero must be zero
+    assert D.worst_tile(z, z) == 0.0 and D.worst_tile(e, z) == np.inf
+
+
+def test_activation_mirror_backward_matches_finite_differences():
+    """activate_f64 and dpre_norm_f64 together are the backward of l2_normalize o dropout o leaky_relu: <dpre, direction> against
+    central differences of <z(pre), dz>"""
+    rng = np.random.default_rng(8)
+    n, d = 5, 7
+    pre = rng.standard_normal((n, d)).astype(np.float32).astype(np.float64); mask = (rng.random((n, d)) >= 0.2).astype(np.float64)
+    dz = rng.standard_normal((n, d))
+    _, z, inv, gate = D.activate_f64(pre, mask, 0.9)
+    dpre = D.dpre_norm_f64(dz, z, 0, None, inv, gate, d)
+    worst = 0.0
+    for _ in range(6):
+        dirn = rng.standard_normal((n, d)); h = 1e-6
+        num = ((D.activate_f64(pre + h * dirn, mask, 0.9)[1] - D.activate_f64(pre - h * dirn, mask, 0.9)[1]) * dz).sum() / (2 * h)
+        worst = max(worst, abs(num - (dpre * dirn).sum()) / abs(num))
+    check("activation mirror: analytic vs central differences", worst, 1e-6)
