@@ -956,6 +956,78 @@ int qrec_sorec_relation_pass(double *d_P, double *d_Z, int32_t d, int32_t ld, co
                              double *d_slots, void *stream);
 int qrec_loss_fold(double *d_running, const double *d_slots, int64_t n, void *stream);
 
+/* ---- CDAE: model/ranking/CDAE.py (csrc/autoencoder.hip) -----------------------------------------------------------------
+ * The denoising auto-encoder over a whole user row, evaluated only where the reference's dense batch x n_items arithmetic is
+ * non-zero.  fp32; tables [rows][ld] with ld a multiple of 32 and columns [nh, ld) zero; the decoder weight is ITEM-MAJOR
+ * ([n_items][ld], the transpose of the reference's variable).  Supported width: ld <= QREC_CDAE_MAX_LD, i.e. nh <= 256 --
+ * a wider call returns QREC_ERR_UNSUPPORTED.  No float atomics: every sum has one order (list order inside a batch row, then
+ * batch-row order), two launches give the same bits.  One batch of B rows (users d_users[b]) is described by
+ *   the INPUT list: CSR over batch rows (d_in_ptr int32 [B+1], d_in_item, d_in_val) of the kept inputs (mask = 1 and rated),
+ *     item ids ascending inside a row, and its item-major view (d_in_cptr [n_items+1], d_in_crow, d_in_cval), rows ascending;
+ *   the LIVE list: CSR (d_lv_ptr, d_lv_item, d_lv_label 1 = positive / 0 = sampled negative) of the loss positions with
+ *     mask = 1, ascending, and its item-major view (d_lv_cptr, d_lv_crow, d_lv_cslot = index of the entry in the CSR).
+ *   Ids outside their table are skipped, never dereferenced.
+ * qrec_cdae_encode:  h_b = sigmoid(sum x_bi Wenc[i] + benc + V[u_b]) summed in list order; h's padding columns are zero.
+ * qrec_cdae_decode:  per live slot s = h_b . Wdec[i] + bdec[i], y = sigmoid(s), y^ = max(1e-6, y); the term is -log y^
+ *   (positive) or -log(1 - y^) (negative), d_g[slot] = d term / d s / (B n_items) with the maximum's gradient passed only
+ *   where y >= 1e-6; the workspace receives dh_b = sum g Wdec[i] as QREC_CDAE_SPLIT partial rows per batch row (each the
+ *   in-order sum of a contiguous share of the row's slots) and the partial loss sums.
+ * qrec_cdae_hidden_bwd:  dz_b = dh_b h_b (1 - h_b) (partials added in order), d_gbenc = sum_b dz_b, and
+ *   d_gV[u_b] += dz_b + reg V[u_b] PER OCCURRENCE of a user (d_gV [n_users][ld] is zeroed first).
+ * qrec_cdae_weight_grads: over the item-major views  gWdec[i] = sum g_bi h_b, gbdec[i] = sum g_bi, gWenc[i] = sum x_bi dz_b;
+ *   rows of items absent from a view are written as exact zeros.  (reg * theta of Wenc, Wdec, benc, bdec: qrec_adam_step's grad_l2.)
+ * qrec_cdae_loss: after decode and hidden_bwd of the same batch,  *d_loss = sum of the terms / (B n_items)
+ *   + reg/2 (sum theta^2 over the n_theta contiguous floats of the four weight variables + sum_b |V[u_b]|^2).
+ * Workspace: qrec_cdae_workspace_bytes(B, ld), shared by the three calls of a step. */
+#define QREC_CDAE_MAX_LD 256
+#define QREC_CDAE_SPLIT 8
+#define QREC_CDAE_REG_BLOCKS 256
+int qrec_cdae_workspace_bytes(int32_t B, int32_t ld, int64_t *bytes);
+int qrec_cdae_encode(const float *d_Wenc, const float *d_benc, const float *d_V, int32_t n_items, int32_t n_users, int32_t nh,
+                     int32_t ld, const int32_t *d_users, int32_t B, const int32_t *d_in_ptr, const int32_t *d_in_item,
+                     const float *d_in_val, float *d_h, void *stream);
+int qrec_cdae_decode(const float *d_Wdec, const float *d_bdec, int32_t n_items, int32_t nh, int32_t ld, const float *d_h, int32_t B,
+                     const int32_t *d_lv_ptr, const int32_t *d_lv_item, const int32_t *d_lv_label, float *d_g, void *d_ws,
+                     void *stream);
+int qrec_cdae_hidden_bwd(const float *d_h, const float *d_V, int32_t n_users, int32_t nh, int32_t ld, const int32_t *d_users, int32_t B,
+                         float reg, void *d_ws, float *d_dz, float *d_gbenc, float *d_gV, void *stream);
+int qrec_cdae_weight_grads(const float *d_h, const float *d_dz, const float *d_g, int32_t n_items, int32_t nh, int32_t ld, int32_t B,
+                           int64_t n_live, const int32_t *d_lv_cptr, const int32_t *d_lv_crow, const int32_t *d_lv_cslot,
+                           const int32_t *d_in_cptr, const int32_t *d_in_crow, const float *d_in_cval, float *d_gWdec, float *d_gbdec,
+                           float *d_gWenc, void *stream);
+int qrec_cdae_loss(const float *d_theta, int64_t n_theta, float reg, int32_t B, int32_t n_items, int32_t ld, void *d_ws, double *d_loss,
+                   void *stream);
+/* qrec_cdae_draw_batch (throughput mode): one batch drawn and its lists built on the device, in the format above, so the
+ * training calls do not know who fed them.  Same distribution as the reference's loop, not its streams: user of row b,
+ * per_rated * |rated(user)| negatives by rejection against the user's rated row (ascending CSR over all users), and the keep
+ * decision (probability keep_prob) of position (step, row, item) are Philox4x32-10 of (seed, step, position) -- the keep
+ * decision is evaluated only at rated or sampled positions.  Negatives are a set per row (a bitmap over the items), lists come
+ * out ascending.  cap_in / cap_live: capacities of the entry arrays; B * max row count and B * (1 + per_rated) * max row count
+ * always suffice, pointers are clamped to them and no entry is written past them.  d_cand_count (may be null) receives per row
+ * the number of positions whose keep decision was evaluated.  Integer atomics only; the result is a function of the arguments.
+ * Workspace: qrec_cdae_draw_workspace_bytes(B, n_items). */
+int qrec_cdae_draw_workspace_bytes(int32_t B, int32_t n_items, int64_t *bytes);
+int qrec_cdae_draw_batch(const int64_t *d_rated_indptr, const int32_t *d_rated_items, const float *d_rated_vals, int32_t n_users,
+                         int32_t n_items, int32_t B, int32_t per_rated, float keep_prob, uint64_t seed, uint64_t step, int64_t cap_in,
+                         int64_t cap_live, void *d_ws, int32_t *d_users, int32_t *d_in_ptr, int32_t *d_in_item, float *d_in_val,
+                         int32_t *d_in_cptr, int32_t *d_in_crow, float *d_in_cval, int32_t *d_lv_ptr, int32_t *d_lv_item,
+                         int32_t *d_lv_label, int32_t *d_lv_cptr, int32_t *d_lv_crow, int32_t *d_lv_cslot, int32_t *d_cand_count,
+                         void *stream);
+/* qrec_mt_cdae_sample_batch (host): CDAE.py:21-43 on the CPython MT19937 stream -- per batch row user = choice(userList), then
+ * per_rated * |rated(user)| draws of choice(itemList), each redrawn while the user rated it (rated CSR over all users).  Draws
+ * per row in draw order, duplicates kept; the generator is left where the reference's loop leaves it. */
+int qrec_mt_cdae_sample_batch(uint32_t *state625, const int64_t *rated_indptr, const int32_t *rated_items, int32_t n_users,
+                              int32_t n_items, int32_t batch, int32_t per_rated, int32_t *users_out, int64_t *neg_indptr,
+                              int32_t *neg_items, int64_t capacity);
+/* qrec_score_topk's BLOCK route with S = sigmoid(S + d_item_bias[item]) between scoring and masking (CDAE.py:100-105 scores
+ * sigmoid(h W + b), then base/recommender.py sets rated items to 0 -- on logits a rated item would outrank every item with a
+ * negative logit).  fp32; d_U = the hidden rows [.][ld], d_V = the item-major decoder weight.  Scratch: its own size query. */
+int qrec_score_topk_sigmoid_bias_scratch_bytes(int32_t n_items, int32_t n_batch_users, int64_t *bytes);
+int qrec_score_topk_sigmoid_bias(const float *d_U, const float *d_V, const float *d_item_bias, int32_t d, int32_t ld, int32_t n_items,
+                                 const int32_t *d_user_ids, int32_t n_batch_users, const int64_t *d_rated_indptr,
+                                 const int32_t *d_rated_items, int32_t N, void *d_scratch, int32_t *d_ids_out, float *d_scores_out,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,17 @@ _SIGNATURES = {
                               _vp],
     "qrec_sorec_relation_pass": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _f64, _f64, _f64, _vp, _vp],
     "qrec_loss_fold": [_vp, _vp, _i64, _vp],
+    "qrec_cdae_workspace_bytes": [_i32, _i32, _vp],
+    "qrec_cdae_encode": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "qrec_cdae_decode": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "qrec_cdae_hidden_bwd": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp],
+    "qrec_cdae_weight_grads": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "qrec_cdae_loss": [_vp, _i64, _f32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "qrec_cdae_draw_workspace_bytes": [_i32, _i32, _vp],
+    "qrec_cdae_draw_batch": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _u64, _u64, _i64, _i64] + [_vp] * 16,
+    "qrec_mt_cdae_sample_batch": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64],
+    "qrec_score_topk_sigmoid_bias_scratch_bytes": [_i32, _i32, _vp],
+    "qrec_score_topk_sigmoid_bias": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"qrec_last_error": C.c_char_p, "qrec_ratings_rows": C.c_int64, "qrec_ratings_count": C.c_int32,
              "qrec_ratings_names_bytes": C.c_int64, "qrec_ratings_free": None}
@@ -458,10 +469,13 @@ class DeviceSlice(DeviceBuffer):
     """Non-owning window [offset, offset + prod(shape)) (elements) of a DeviceBuffer: several small tables carved out
     of one allocation so that one kernel launch can cover all of them (e.g. the four NGCF weight matrices in Adam)."""
 
-    def __init__(self, owner: DeviceBuffer, offset_elems: int, shape):
+    def __init__(self, owner: DeviceBuffer, offset_elems: int, shape, dtype=None):
+        """``dtype``: read the window as another type of the owner's item size (int32 staging holding float32 values)"""
         self.owner = owner
         self.shape = tuple(int(x) for x in (shape if isinstance(shape, (tuple, list)) else (shape,)))
-        self.dtype = owner.dtype
+        self.dtype = owner.dtype if dtype is None else np.dtype(dtype)
+        if self.dtype.itemsize != owner.dtype.itemsize:
+            raise ValueError("DeviceSlice: dtype of another item size than its owner's")
         self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
         if offset_elems < 0 or offset_elems * self.dtype.itemsize + self.nbytes > owner.nbytes:
             raise ValueError("DeviceSlice outside its owner")
@@ -1459,3 +1473,82 @@ def sorec_relation_pass(d_P, d_Z, d: int, ld: int, d_rel_u, d_rel_v, d_rel_t, d_
 def loss_fold(d_running, d_slots, n: int, stream=None):
     """*d_running += slots[0], += slots[1], ... one after the other"""
     _check(load().qrec_loss_fold(_dp(d_running), _dp(d_slots), n, _sh(stream)))
+
+
+# ---- CDAE (csrc/autoencoder.hip; the list format is described in include/qrec_hip.h) ----------------------------------------
+CDAE_MAX_LD = 256
+
+
+def cdae_workspace_bytes(B: int, ld: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_cdae_workspace_bytes(B, ld, C.byref(out)))
+    return out.value
+
+
+def cdae_encode(d_Wenc, d_benc, d_V, n_items: int, n_users: int, nh: int, ld: int, d_users, B: int, d_in_ptr, d_in_item, d_in_val, d_h,
+                stream=None):
+    _check(load().qrec_cdae_encode(_dp(d_Wenc), _dp(d_benc), _dp(d_V), n_items, n_users, nh, ld, _dp(d_users), B, _dp(d_in_ptr),
+                                   _dp(d_in_item), _dp(d_in_val), _dp(d_h), _sh(stream)))
+
+
+def cdae_decode(d_Wdec, d_bdec, n_items: int, nh: int, ld: int, d_h, B: int, d_lv_ptr, d_lv_item, d_lv_label, d_g, d_ws, stream=None):
+    _check(load().qrec_cdae_decode(_dp(d_Wdec), _dp(d_bdec), n_items, nh, ld, _dp(d_h), B, _dp(d_lv_ptr), _dp(d_lv_item), _dp(d_lv_label),
+                                   _dp(d_g), _dp(d_ws), _sh(stream)))
+
+
+def cdae_hidden_bwd(d_h, d_V, n_users: int, nh: int, ld: int, d_users, B: int, reg: float, d_ws, d_dz, d_gbenc, d_gV, stream=None):
+    _check(load().qrec_cdae_hidden_bwd(_dp(d_h), _dp(d_V), n_users, nh, ld, _dp(d_users), B, reg, _dp(d_ws), _dp(d_dz), _dp(d_gbenc),
+                                       _dp(d_gV), _sh(stream)))
+
+
+def cdae_weight_grads(d_h, d_dz, d_g, n_items: int, nh: int, ld: int, B: int, n_live: int, d_lv_cptr, d_lv_crow, d_lv_cslot, d_in_cptr,
+                      d_in_crow, d_in_cval, d_gWdec, d_gbdec, d_gWenc, stream=None):
+    _check(load().qrec_cdae_weight_grads(_dp(d_h), _dp(d_dz), _dp(d_g), n_items, nh, ld, B, n_live, _dp(d_lv_cptr), _dp(d_lv_crow),
+                                         _dp(d_lv_cslot), _dp(d_in_cptr), _dp(d_in_crow), _dp(d_in_cval), _dp(d_gWdec), _dp(d_gbdec),
+                                         _dp(d_gWenc), _sh(stream)))
+
+
+def cdae_loss(d_theta, n_theta: int, reg: float, B: int, n_items: int, ld: int, d_ws, d_loss, stream=None):
+    _check(load().qrec_cdae_loss(_dp(d_theta), n_theta, reg, B, n_items, ld, _dp(d_ws), _dp(d_loss), _sh(stream)))
+
+
+def cdae_draw_workspace_bytes(B: int, n_items: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_cdae_draw_workspace_bytes(B, n_items, C.byref(out)))
+    return out.value
+
+
+def cdae_draw_batch(d_rated_indptr, d_rated_items, d_rated_vals, n_users: int, n_items: int, B: int, per_rated: int, keep_prob: float,
+                    seed: int, step: int, cap_in: int, cap_live: int, d_ws, L, d_cand_count=None, stream=None):
+    """one batch drawn on the device (Philox of seed, step, position) into the thirteen device arrays of ``L`` (a BatchLists)"""
+    _check(load().qrec_cdae_draw_batch(_dp(d_rated_indptr), _dp(d_rated_items), _dp(d_rated_vals), n_users, n_items, B, per_rated, keep_prob,
+                                       seed & (2 ** 64 - 1), step, cap_in, cap_live, _dp(d_ws), _dp(L.users), _dp(L.in_ptr), _dp(L.in_item),
+                                       _dp(L.in_val), _dp(L.in_cptr), _dp(L.in_crow), _dp(L.in_cval), _dp(L.lv_ptr), _dp(L.lv_item),
+                                       _dp(L.lv_label), _dp(L.lv_cptr), _dp(L.lv_crow), _dp(L.lv_cslot), _dp(d_cand_count), _sh(stream)))
+
+
+def mt_cdae_sample_batch(state625: np.ndarray, rated_indptr, rated_items, n_items: int, batch: int, per_rated: int = 5):
+    """CDAE.py:21-43 on the CPython stream (``state625`` is advanced in place): (users int32 [batch], neg_indptr int64 [batch + 1],
+    neg_items int32) -- every row's ``per_rated * |rated|`` draws in draw order, duplicates kept"""
+    _req(state625, np.uint32, "state625"); _req(rated_indptr, np.int64, "rated_indptr"); _req(rated_items, np.int32, "rated_items")
+    n_users = rated_indptr.size - 1
+    # users are drawn with replacement: the heaviest user may fill every row of the batch
+    cap = int(per_rated) * int(batch) * int(np.diff(rated_indptr).max()) if n_users else 0
+    users = np.empty(batch, np.int32); ptr = np.empty(batch + 1, np.int64); neg = np.empty(max(cap, 1), np.int32)
+    _check(load().qrec_mt_cdae_sample_batch(_hp(state625), _hp(rated_indptr), _hp(rated_items), n_users, n_items, batch, per_rated,
+                                            _hp(users), _hp(ptr), _hp(neg), cap))
+    return users, ptr, neg[:ptr[-1]].copy()
+
+
+def score_topk_sigmoid_bias_scratch_bytes(n_items: int, n_batch_users: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_score_topk_sigmoid_bias_scratch_bytes(n_items, n_batch_users, C.byref(out)))
+    return out.value
+
+
+def score_topk_sigmoid_bias(d_U, d_V, d_item_bias, d: int, ld: int, n_items: int, d_user_ids, n_batch_users: int, d_rated_indptr,
+                            d_rated_items, N: int, d_scratch, d_ids_out, d_scores_out, stream=None):
+    """qrec_score_topk's block route with S = sigmoid(S + bias[item]) between scoring and masking (fp32)"""
+    _check(load().qrec_score_topk_sigmoid_bias(_dp(d_U), _dp(d_V), _dp(d_item_bias), d, ld, n_items, _dp(d_user_ids), n_batch_users,
+                                               _dp(d_rated_indptr), _dp(d_rated_items), N, _dp(d_scratch), _dp(d_ids_out),
+                                               _dp(d_scores_out), _sh(stream)))

@@ -46,6 +46,10 @@ int ordered_ws_bytes(int64_t n_slots, int ld, int64_t *bytes);
 int ordered_ws_carve(void *ws, int64_t ws_bytes, int64_t n_slots, int ld, OrderedScatterWs *w);
 int ordered_scatter_run(const OrderedScatterWs &w, int64_t n_slots, int ld, int64_t class_size, float *out, hipStream_t st);
 
+// S = sigmoid(S + bias[item]) over the evaluation's transposed [n_items][b_pad] fp32 score block (autoencoder.hip; the pass
+// qrec_score_topk_sigmoid_bias runs between scoring and masking)
+int score_block_sigmoid_bias(float *S_T, const float *bias, int n_items, int b_pad, hipStream_t st);
+
 // ---- buffer resources: the only way to get 16-byte loads/stores with an explicit cache
 // policy (sc1 = bypass the non-coherent per-XCD caches) and compiler-tracked waitcnts.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

@@ -1413,7 +1413,7 @@ __global__ void scatter_rows_kernel(const int32_t *__restrict__ flagged_list, in
 template <typename T>
 int run_score_topk(const void *U, const void *V, int d, int ld, int n_items, const int32_t *user_ids,
                    int n_b, const int64_t *rated_indptr, const int32_t *rated_items, int K, void *scratch,
-                   int32_t *ids_out, void *scores_out, hipStream_t st) {
+                   int32_t *ids_out, void *scores_out, hipStream_t st, const float *item_bias = nullptr) {
     constexpr int TILE = sizeof(T) == 4 ? 32 : 16;         // items per MFMA tile
     constexpr int UTILE = sizeof(T) == 4 ? 64 : 16;        // users per wavefront (fp32: two 32-user tiles)
     const int b_pad = (n_b + 63) / 64 * 64;
@@ -1433,6 +1433,12 @@ int run_score_topk(const void *U, const void *V, int d, int ld, int n_items, con
         hipLaunchKernelGGL(score_kernel_f64, grid, dim3(256), 0, st, (const double *)U, (const double *)V, ld,
                            n_items, user_ids, n_b, b_pad, per_wave, S_T);
     QREC_LAUNCH_CHECK();
+    if constexpr (sizeof(T) == 4) {
+        if (item_bias) {       // qrec_score_topk_sigmoid_bias: S = sigmoid(S + bias[item]) before the rated items are set to 0
+            const int rc = qrec::score_block_sigmoid_bias(S_T, item_bias, n_items, b_pad, st);
+            if (rc != QREC_OK) return rc;
+        }
+    }
     if (rated_indptr) {
         hipLaunchKernelGGL(mask_kernel<T>, dim3((unsigned)((n_b + 3) / 4)), dim3(256), 0, st, user_ids, n_b,
                            rated_indptr, rated_items, b_pad, S_T, TILE, 1, (int64_t)64, (int64_t)1);
@@ -1922,6 +1928,26 @@ int qrec_score_topk(const void *d_U, const void *d_V, int dtype, int32_t d, int3
                                         d_rated_items, K, d_scratch, d_ids_out, d_scores_out, st)
                : run_score_topk<float>(d_U, d_V, d, ld, n_items, d_user_ids, n_batch_users, d_rated_indptr,
                                        d_rated_items, K, d_scratch, d_ids_out, d_scores_out, st);
+}
+
+int qrec_score_topk_sigmoid_bias_scratch_bytes(int32_t n_items, int32_t n_batch_users, int64_t *bytes) {
+    QREC_REQUIRE(bytes && n_items >= 0 && n_batch_users >= 0, "qrec_score_topk_sigmoid_bias_scratch_bytes: bad arguments");
+    *bytes = (int64_t)block_path_bytes(4, n_items, n_batch_users);
+    return QREC_OK;
+}
+
+int qrec_score_topk_sigmoid_bias(const float *d_U, const float *d_V, const float *d_item_bias, int32_t d, int32_t ld, int32_t n_items,
+                                 const int32_t *d_user_ids, int32_t n_batch_users, const int64_t *d_rated_indptr,
+                                 const int32_t *d_rated_items, int32_t K, void *d_scratch, int32_t *d_ids_out, float *d_scores_out,
+                                 void *stream) {
+    QREC_REQUIRE(d_U && d_V && d_item_bias && d_user_ids && d_scratch && d_ids_out && d_scores_out, "qrec_score_topk_sigmoid_bias: null argument");
+    QREC_REQUIRE(d >= 1 && ld >= d && n_items >= 1 && n_batch_users >= 0, "qrec_score_topk_sigmoid_bias: bad sizes");
+    QREC_REQUIRE(ld % 32 == 0, "qrec_score_topk_sigmoid_bias: the row stride must be a multiple of 32 floats, pad columns zero (got ld=%d)", ld);
+    QREC_REQUIRE(K >= 1 && K <= 100, "qrec_score_topk_sigmoid_bias: N must be in 1..100 (base/recommender.py:132-134)");
+    QREC_REQUIRE((d_rated_indptr == nullptr) == (d_rated_items == nullptr), "qrec_score_topk_sigmoid_bias: rated CSR incomplete");
+    if (n_batch_users == 0) return QREC_OK;
+    return run_score_topk<float>(d_U, d_V, d, ld, n_items, d_user_ids, n_batch_users, d_rated_indptr, d_rated_items, K, d_scratch,
+                                 d_ids_out, d_scores_out, as_stream(stream), d_item_bias);
 }
 
 int qrec_rank_hits(const int32_t *d_ids, int32_t n_batch_users, int32_t row_stride, int32_t n_cut,

@@ -24,15 +24,18 @@ class DeviceRanker:
         numpy-path models, fp32 for the TF-path ones); ``rated`` = train items per user."""
         if U.dtype != V.dtype or U.dtype not in (np.float32, np.float64):
             raise TypeError("U and V must both be float32 or both float64")
-        self.dtype = U.dtype
-        self.code = capi.F64 if self.dtype == np.float64 else capi.F32
-        self.d = U.shape[1]
-        assert V.shape[1] == self.d
-        self.n_users, self.n_items = U.shape[0], V.shape[0]
-        slot = 16 if self.dtype == np.float64 else 32          # MFMA k-slot width of the scoring kernels
-        self.ld = -(-self.d // slot) * slot                     # zero-padded row stride (include/qrec_hip.h)
+        assert V.shape[1] == U.shape[1]
+        slot = 16 if U.dtype == np.float64 else 32              # MFMA k-slot width of the scoring kernels
+        self._init_state(U.dtype, U.shape[1], -(-U.shape[1] // slot) * slot, U.shape[0], V.shape[0], rated)
         self.dU = DeviceBuffer.from_numpy(self._pad(U))
         self.dV = DeviceBuffer.from_numpy(self._pad(V))
+
+    def _init_state(self, dtype, d: int, ld: int, n_users: int, n_items: int, rated: CSR | None):
+        """everything a ranker holds but its score tables (dU, dV); ``ld`` = zero-padded row stride (include/qrec_hip.h).
+        Subclasses whose tables already sit on the device start here."""
+        self.dtype = np.dtype(dtype)
+        self.code = capi.F64 if self.dtype == np.float64 else capi.F32
+        self.d, self.ld, self.n_users, self.n_items = d, ld, n_users, n_items
         self._scratch = self._d_ids = self._d_sc = None
         self._cap = (0, 0)
         self.rated = None
@@ -63,6 +66,14 @@ class DeviceRanker:
         self.test = (DeviceBuffer.from_numpy(srt.indptr.astype(np.int64)),
                      DeviceBuffer.from_numpy(srt.indices.astype(np.int32) if srt.indices.size else np.zeros(1, np.int32)))
 
+    def _scratch_bytes(self, n_batch_users: int, N: int) -> int:
+        return capi.score_topk_scratch_bytes(self.code, self.n_items, n_batch_users, self.ld, N)
+
+    def _score_topk(self, d_users, n: int, N: int, scratch, d_ids, d_sc):
+        capi.score_topk(self.dU, self.dV, self.code, self.d, self.ld, self.n_items, d_users, n,
+                        self.rated[0] if self.rated else None, self.rated[1] if self.rated else None,
+                        N, scratch, d_ids, d_sc)
+
     def topk(self, user_ids: np.ndarray, N: int, cuts=None, want_lists: bool = True):
         """(ids int32 [n, N], scores [n, N]) in the reference's order (descending score,
         heap order among ties).  With ``cuts`` (list of list lengths <= N; needs ``set_test``) a third
@@ -86,13 +97,13 @@ class DeviceRanker:
             raise ValueError("user id out of range")
         # users per call: as many as the scratch budget allows (fused route: ~15 KB per user at the Yelp2018 shape,
         # block route: the whole score column, 150 KB)
-        per_user = capi.score_topk_scratch_bytes(self.code, self.n_items, 4096, self.ld, N) // 4096
+        per_user = self._scratch_bytes(4096, N) // 4096
         batch = int(max(64, min(n, (_SCRATCH_BUDGET // max(per_user, 1)) // 64 * 64)))
         nb = min(batch, n)
         # kept across calls (per-epoch evaluation).  The byte count depends on the evaluation route the library picks from
         # QREC_EVAL_* at every call (bf16 copies, list capacity): it is asked again each time and the scratch re-made when the
         # cached one is too small for the route now in force
-        need = capi.score_topk_scratch_bytes(self.code, self.n_items, nb, self.ld, N)
+        need = self._scratch_bytes(nb, N)
         if self._cap[0] < nb or self._cap[1] != N or self._scratch.nbytes < need:
             self._scratch = DeviceBuffer(need, np.uint8)
             self._d_ids = DeviceBuffer((nb, N), np.int32); self._d_sc = DeviceBuffer((nb, N), self.dtype)
@@ -103,9 +114,7 @@ class DeviceRanker:
         for s in range(0, n, batch):
             chunk = user_ids[s:s + batch]
             d_users = DeviceBuffer.from_numpy(chunk)
-            capi.score_topk(self.dU, self.dV, self.code, self.d, self.ld, self.n_items, d_users, chunk.size,
-                            self.rated[0] if self.rated else None, self.rated[1] if self.rated else None,
-                            N, scratch, d_ids, d_sc)
+            self._score_topk(d_users, chunk.size, N, scratch, d_ids, d_sc)
             if want_lists:
                 ids[s:s + chunk.size] = d_ids.numpy()[:chunk.size]
                 scores[s:s + chunk.size] = d_sc.numpy()[:chunk.size]
@@ -115,6 +124,27 @@ class DeviceRanker:
                     capi.rank_hits(d_ids, chunk.size, N, c, d_users, self.test[0], self.test[1], d_disc, d_hits, d_dcg)
                     hits[s:s + chunk.size] = d_hits.numpy(); dcg[s:s + chunk.size] = d_dcg.numpy()
         return (ids, scores) if cuts is None else (ids, scores, per_cut)
+
+
+class SigmoidBiasRanker(DeviceRanker):
+    """scores = sigmoid(V . U[user] + bias[item]), rated train items then set to 0 (CDAE.py:100-105 + base/recommender.py:147-149):
+    the block route of the scoring with the element-wise pass in between (qrec_score_topk_sigmoid_bias).  The tables are the
+    trainer's own device buffers -- hidden rows of ALL users [n_users][ld], the item-major decoder weight, the item bias; nothing
+    is uploaded.  ``topk`` slices the users to the scratch budget as the base class does."""
+
+    def __init__(self, d_U, d_V, d_bias, n_users: int, n_items: int, d: int, ld: int, rated: CSR | None = None):
+        self._init_state(np.float32, d, ld, n_users, n_items, rated)
+        self.dU, self.dV, self.d_bias = d_U, d_V, d_bias
+
+    def update_tables(self, d_U, d_V, d_bias):
+        self.dU, self.dV, self.d_bias = d_U, d_V, d_bias
+
+    def _scratch_bytes(self, n_batch_users: int, N: int) -> int:
+        return capi.score_topk_sigmoid_bias_scratch_bytes(self.n_items, n_batch_users)
+
+    def _score_topk(self, d_users, n: int, N: int, scratch, d_ids, d_sc):
+        capi.score_topk_sigmoid_bias(self.dU, self.dV, self.d_bias, self.d, self.ld, self.n_items, d_users, n,
+                                     self.rated[0] if self.rated else None, self.rated[1] if self.rated else None, N, scratch, d_ids, d_sc)
 
 
 def ranking_measure_strings(test_lens, per_n: dict, Ns) -> list:
