@@ -1028,6 +1028,75 @@ int qrec_score_topk_sigmoid_bias(const float *d_U, const float *d_V, const float
                                  const int32_t *d_rated_items, int32_t N, void *d_scratch, int32_t *d_ids_out, float *d_scores_out,
                                  void *stream);
 
+/* ---- IRGAN: model/ranking/IRGAN.py (csrc/irgan.hip) ------------------------------------------------------------------------
+ * A categorical distribution over the whole item table per user (tempered softmax, its CDF, many draws from it), the reward of
+ * the drawn items, the policy-gradient step whose gradient is dense over the item table with TF's dense Adam, and the
+ * discriminator's per-slot gradient rows.  Both towers score P[u] . Q[i] + b[i].
+ * fp32 tables [rows][ld], ld one of 32 / 64 / 128 / 256, padding columns zero and kept zero.  An ITEM table carries its bias in
+ * column d of the row ([Q | b]: d + 1 <= ld) and a user's row is read as [P[u] | 1], so one dot product is the logit and the
+ * bias trains as one more column; a user table keeps columns >= d zero.  ld > QREC_IRGAN_MAX_LD or d + 1 > ld returns
+ * QREC_ERR_UNSUPPORTED.  Ids outside a table are skipped, never dereferenced.  No float atomics: every sum has one order and two
+ * launches give the same bits.  Plain launches on the caller's stream, no host read-back.
+ *
+ * qrec_irgan_row_weights: for the B users d_users[b] (positives: ascending CSR d_pos_indptr int64 [n_users + 1] / d_pos_items over
+ *   ALL users), z_bj = ([P[u_b] | 1] . Qb[j]) / temperature into d_z [B][n_items], then with m = max_j z_bj
+ *     QREC_IRGAN_NEGATIVES (get_data):  w = exp(z - m), 0 at the positives; d_p (may be null) receives exp(z - m) at every item;
+ *     QREC_IRGAN_MIXTURE (generator):   p = exp(z - m) / sum_j exp(z_j - m) into d_p,  w = pn = (1 - sample_lambda) p, plus
+ *                                       sample_lambda / |pos| at the positives.
+ *   d_w [B][n_items] receives w and d_csum [B][ceil(n_items / QREC_IRGAN_CHUNK)] the INCLUSIVE prefix sums of w at the chunk
+ *   ends, accumulated in fp64 in index order (inside a chunk, then chunk after chunk); the last one is the row total.
+ *   The reference does not subtract m; the results differ only where its exp overflows float32 (z / T > 88).
+ *   Workspace: qrec_irgan_row_workspace_bytes(B, n_items).  B <= 65535.
+ * qrec_irgan_draw: row b takes the draws [d_draw_ptr[b], d_draw_ptr[b + 1]) (int64 [B + 1], n_draws in all).  Draw s of row b with
+ *   uniform x in [0, 1) is the first item whose CDF value exceeds x (numpy's searchsorted(cdf, x, 'right') in np.random.choice):
+ *   a binary search over the chunk sums for x * total, then the walk inside the chunk in the order its sum was formed, so a draw
+ *   never lands on an item of zero weight.  x = d_uniforms[s], or, when d_uniforms is null, the 53-bit uniform of
+ *   Philox4x32-10 keyed by (seed, step, row, index inside the row).  A row whose total is 0 draws -1.
+ * qrec_irgan_uniforms: the uniforms qrec_irgan_draw uses when d_uniforms is null, d_out [n_draws].
+ * qrec_irgan_reward: per sample  2 (sigmoid(x) - 1/2) d_p[b][i] / d_w[b][i]  with x = [P[u_b] | 1] . Qb[i] (P, Qb: the discriminator's),
+ *   in float32 in that order, as the reference's graph forms it (its recorded losses carry the cancellation near x = 0).
+ * qrec_irgan_gen_step (one user): with c_j = sum of the rewards of the samples equal to j in SAMPLE order (stable radix sort of
+ *   (item, index) + walk), n_j their number, R = sum_k reward_k and K samples,  g_j = -(c_j - R p_j) / K  for every item,
+ *     G[j] = g_j [P[u] | 1] + reg n_j Qb[j]     applied to Qb[j] by Adam in the same pass (the arithmetic of qrec_adam_step, alpha
+ *     from the host) when apply != 0 -- no [n_items][ld] gradient exists unless d_gQ (may be null) asks for it; d_g (may be null)
+ *     receives g;  d_gP[user] = sum_j g_j Qb[j][:d] (rows as read BEFORE their update; 64 items per workgroup in item order, then
+ *     workgroup order) + reg P[user], the other rows of d_gP [n_users][ld] are not touched (keep them zero and hand the buffer to
+ *     qrec_adam_step);  *d_loss (may be null) = -(1/K) sum_k log p[i_k] reward_k + reg (|P[u]|^2 + sum_k |Qb[i_k]|^2) / 2.
+ *   Workspace: qrec_irgan_gen_workspace_bytes(n_items, ld, K).
+ * qrec_irgan_dis_slots: per slot s (user d_u[s], item d_i[s], label d_label[s]) x = [P[u] | 1] . Qb[i], dz = sigmoid(x) - label,
+ *     d_slotP[s] = dz Q[i] + B reg P[u],  d_slotQ[s] = dz [P[u] | 1] + B reg Qb[i]   (the reference minimises a [B] vector: the
+ *     regulariser enters once per slot, B times over), d_keyP / d_keyQ = the destination rows (-1: a bad id) for
+ *     qrec_scatter_add_rows_ordered, d_dz (may be null), d_terms [B] scratch, and
+ *     *d_loss = sum_s (max(x, 0) - x label + log1p(exp(-|x|))) + B reg sum_s (|P[u]|^2 + |Qb[i]|^2) / 2.
+ * qrec_irgan_assemble_rows: get_data's rows for a block of users on the device: row b owns [d_row_ptr[b], d_row_ptr[b + 1]) --
+ *   its positives in CSR order with label 1, then its draws with label 0. */
+#define QREC_IRGAN_MAX_LD 256
+#define QREC_IRGAN_CHUNK 64
+#define QREC_IRGAN_NEGATIVES 0
+#define QREC_IRGAN_MIXTURE 1
+int qrec_irgan_row_workspace_bytes(int32_t B, int32_t n_items, int64_t *bytes);
+int qrec_irgan_row_weights(const float *d_P, const float *d_Q, int32_t n_users, int32_t n_items, int32_t d, int32_t ld,
+                           const int32_t *d_users, int32_t B, const int64_t *d_pos_indptr, const int32_t *d_pos_items, int32_t mode,
+                           float temperature, float sample_lambda, float *d_z, float *d_w, float *d_p, double *d_csum, void *d_ws,
+                           void *stream);
+int qrec_irgan_draw(const float *d_w, const double *d_csum, int32_t n_items, int32_t B, const int64_t *d_draw_ptr, int64_t n_draws,
+                    const double *d_uniforms, uint64_t seed, uint64_t step, int32_t *d_samples, void *stream);
+int qrec_irgan_uniforms(int32_t B, const int64_t *d_draw_ptr, int64_t n_draws, uint64_t seed, uint64_t step, double *d_out, void *stream);
+int qrec_irgan_reward(const float *d_P, const float *d_Q, int32_t n_users, int32_t n_items, int32_t d, int32_t ld, const int32_t *d_users,
+                      int32_t B, const int64_t *d_draw_ptr, int64_t n_draws, const int32_t *d_samples, const float *d_p, const float *d_w,
+                      float *d_reward, void *stream);
+int qrec_irgan_gen_workspace_bytes(int32_t n_items, int32_t ld, int64_t K, int64_t *bytes);
+int qrec_irgan_gen_step(const float *d_P, float *d_Q, float *d_mQ, float *d_vQ, int32_t n_users, int32_t n_items, int32_t d, int32_t ld,
+                        int32_t user, const int32_t *d_samples, const float *d_reward, int64_t K, const float *d_p, float reg, int32_t apply,
+                        float alpha, float beta1, float beta2, float eps, float *d_gP, float *d_g, float *d_gQ, double *d_loss, void *d_ws,
+                        int64_t ws_bytes, void *stream);
+int qrec_irgan_dis_slots(const float *d_P, const float *d_Q, int32_t n_users, int32_t n_items, int32_t d, int32_t ld, const int32_t *d_u,
+                         const int32_t *d_i, const float *d_label, int32_t B, float reg, float *d_slotP, float *d_slotQ, int32_t *d_keyP,
+                         int32_t *d_keyQ, float *d_dz, double *d_terms, double *d_loss, void *stream);
+int qrec_irgan_assemble_rows(const int32_t *d_users, int32_t n_users, int32_t B, const int64_t *d_pos_indptr, const int32_t *d_pos_items,
+                             const int64_t *d_draw_ptr, const int32_t *d_samples, const int64_t *d_row_ptr, int64_t n_rows, int32_t *d_out_u,
+                             int32_t *d_out_i, float *d_out_label, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,16 @@ _SIGNATURES = {
     "qrec_mt_cdae_sample_batch": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64],
     "qrec_score_topk_sigmoid_bias_scratch_bytes": [_i32, _i32, _vp],
     "qrec_score_topk_sigmoid_bias": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    "qrec_irgan_row_workspace_bytes": [_i32, _i32, _vp],
+    "qrec_irgan_row_weights": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "qrec_irgan_draw": [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _u64, _u64, _vp, _vp],
+    "qrec_irgan_uniforms": [_i32, _vp, _i64, _u64, _u64, _vp, _vp],
+    "qrec_irgan_reward": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "qrec_irgan_gen_workspace_bytes": [_i32, _i32, _i64, _vp],
+    "qrec_irgan_gen_step": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _f32, _i32, _f32, _f32, _f32, _f32, _vp, _vp,
+                            _vp, _vp, _vp, _i64, _vp],
+    "qrec_irgan_dis_slots": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "qrec_irgan_assemble_rows": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"qrec_last_error": C.c_char_p, "qrec_ratings_rows": C.c_int64, "qrec_ratings_count": C.c_int32,
              "qrec_ratings_names_bytes": C.c_int64, "qrec_ratings_free": None}
@@ -1552,3 +1562,62 @@ def score_topk_sigmoid_bias(d_U, d_V, d_item_bias, d: int, ld: int, n_items: int
     _check(load().qrec_score_topk_sigmoid_bias(_dp(d_U), _dp(d_V), _dp(d_item_bias), d, ld, n_items, _dp(d_user_ids), n_batch_users,
                                                _dp(d_rated_indptr), _dp(d_rated_items), N, _dp(d_scratch), _dp(d_ids_out),
                                                _dp(d_scores_out), _sh(stream)))
+
+
+# ---- IRGAN (csrc/irgan.hip; the contract is in include/qrec_hip.h) --------------------------------------------------------------
+IRGAN_MAX_LD = 256
+IRGAN_CHUNK = 64
+IRGAN_NEGATIVES, IRGAN_MIXTURE = 0, 1
+
+
+def irgan_row_workspace_bytes(B: int, n_items: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_irgan_row_workspace_bytes(B, n_items, C.byref(out)))
+    return out.value
+
+
+def irgan_row_weights(d_P, d_Q, n_users: int, n_items: int, d: int, ld: int, d_users, B: int, d_pos_indptr, d_pos_items, mode: int,
+                      temperature: float, sample_lambda: float, d_z, d_w, d_p, d_csum, d_ws, stream=None):
+    _check(load().qrec_irgan_row_weights(_dp(d_P), _dp(d_Q), n_users, n_items, d, ld, _dp(d_users), B, _dp(d_pos_indptr), _dp(d_pos_items), mode,
+                                         temperature, sample_lambda, _dp(d_z), _dp(d_w), _dp(d_p), _dp(d_csum), _dp(d_ws), _sh(stream)))
+
+
+def irgan_draw(d_w, d_csum, n_items: int, B: int, d_draw_ptr, n_draws: int, d_uniforms, seed: int, step: int, d_samples, stream=None):
+    """``d_uniforms`` None: the draws take the Philox uniforms of (seed, step, row, index)"""
+    _check(load().qrec_irgan_draw(_dp(d_w), _dp(d_csum), n_items, B, _dp(d_draw_ptr), n_draws, _dp(d_uniforms), seed & (2 ** 64 - 1), step,
+                                  _dp(d_samples), _sh(stream)))
+
+
+def irgan_uniforms(B: int, d_draw_ptr, n_draws: int, seed: int, step: int, d_out, stream=None):
+    _check(load().qrec_irgan_uniforms(B, _dp(d_draw_ptr), n_draws, seed & (2 ** 64 - 1), step, _dp(d_out), _sh(stream)))
+
+
+def irgan_reward(d_P, d_Q, n_users: int, n_items: int, d: int, ld: int, d_users, B: int, d_draw_ptr, n_draws: int, d_samples, d_p, d_w,
+                 d_reward, stream=None):
+    _check(load().qrec_irgan_reward(_dp(d_P), _dp(d_Q), n_users, n_items, d, ld, _dp(d_users), B, _dp(d_draw_ptr), n_draws, _dp(d_samples),
+                                    _dp(d_p), _dp(d_w), _dp(d_reward), _sh(stream)))
+
+
+def irgan_gen_workspace_bytes(n_items: int, ld: int, K: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_irgan_gen_workspace_bytes(n_items, ld, K, C.byref(out)))
+    return out.value
+
+
+def irgan_gen_step(d_P, d_Q, d_mQ, d_vQ, n_users: int, n_items: int, d: int, ld: int, user: int, d_samples, d_reward, K: int, d_p, reg: float,
+                   apply: bool, alpha: float, beta1: float, beta2: float, eps: float, d_gP, d_g, d_gQ, d_loss, d_ws, stream=None):
+    _check(load().qrec_irgan_gen_step(_dp(d_P), _dp(d_Q), _dp(d_mQ), _dp(d_vQ), n_users, n_items, d, ld, user, _dp(d_samples), _dp(d_reward), K,
+                                      _dp(d_p), reg, int(apply), alpha, beta1, beta2, eps, _dp(d_gP), _dp(d_g), _dp(d_gQ), _dp(d_loss), _dp(d_ws),
+                                      d_ws.nbytes, _sh(stream)))
+
+
+def irgan_dis_slots(d_P, d_Q, n_users: int, n_items: int, d: int, ld: int, d_u, d_i, d_label, B: int, reg: float, d_slotP, d_slotQ, d_keyP,
+                    d_keyQ, d_dz, d_terms, d_loss, stream=None):
+    _check(load().qrec_irgan_dis_slots(_dp(d_P), _dp(d_Q), n_users, n_items, d, ld, _dp(d_u), _dp(d_i), _dp(d_label), B, reg, _dp(d_slotP),
+                                       _dp(d_slotQ), _dp(d_keyP), _dp(d_keyQ), _dp(d_dz), _dp(d_terms), _dp(d_loss), _sh(stream)))
+
+
+def irgan_assemble_rows(d_users, n_users: int, B: int, d_pos_indptr, d_pos_items, d_draw_ptr, d_samples, d_row_ptr, n_rows: int, d_out_u,
+                        d_out_i, d_out_label, stream=None):
+    _check(load().qrec_irgan_assemble_rows(_dp(d_users), n_users, B, _dp(d_pos_indptr), _dp(d_pos_items), _dp(d_draw_ptr), _dp(d_samples),
+                                           _dp(d_row_ptr), n_rows, _dp(d_out_u), _dp(d_out_i), _dp(d_out_label), _sh(stream)))
