@@ -132,25 +132,21 @@ struct SolveWs {
     int64_t capacity, seg_stride;
 };
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
 inline int64_t seg_stride_of(int ld) { return ((int64_t)ld * ld + ld + 1 + 31) & ~int64_t(31); }
-inline int64_t solve_fixed_bytes(int64_t n_rows, int ld) {
-    return align256(16) + align256(8 * (n_rows + 1)) + align256(8 * n_rows) + align256(8 * n_rows * ld);
-}
 __host__ __device__ inline int64_t segments_of(int64_t deg) {
     return deg > QREC_ALS_SPLIT_DEGREE ? (deg + QREC_ALS_SEGMENT - 1) / QREC_ALS_SEGMENT : 0;
 }
 
-SolveWs carve(void *ws, int64_t ws_bytes, int64_t n_rows, int ld) {
+// The fixed part of the layout; `partial` is whatever the buffer holds behind it, counted in whole segments.
+SolveWs solve_layout(Carver &c, int64_t ws_bytes, int64_t n_rows, int ld) {
     SolveWs w;
-    char *p = static_cast<char *>(ws);
-    w.status = reinterpret_cast<int *>(p); p += align256(16);
-    w.seg_off = reinterpret_cast<int64_t *>(p); p += align256(8 * (n_rows + 1));
-    w.row_loss = reinterpret_cast<double *>(p); p += align256(8 * n_rows);
-    w.x_new = reinterpret_cast<double *>(p); p += align256(8 * n_rows * ld);
-    w.partial = reinterpret_cast<double *>(p);
+    w.status = c.take<int>(4, 256);
+    w.seg_off = c.take<int64_t>((size_t)(n_rows + 1), 256);
+    w.row_loss = c.take<double>((size_t)n_rows, 256);
+    w.x_new = c.take<double>((size_t)(n_rows * ld), 256);
+    w.partial = c.take<double>(0, 256);
     w.seg_stride = seg_stride_of(ld);
-    w.capacity = (ws_bytes - solve_fixed_bytes(n_rows, ld)) / (8 * w.seg_stride);
+    w.capacity = (ws_bytes - (int64_t)c.bytes()) / (8 * w.seg_stride);
     return w;
 }
 
@@ -356,7 +352,9 @@ extern "C" int qrec_als_solve_workspace_bytes(const int64_t *h_indptr, int64_t n
         QREC_REQUIRE(deg >= 0, "qrec_als_solve_workspace_bytes: indptr decreases at row %lld", (long long)r);
         segs += segments_of(deg);
     }
-    *bytes = solve_fixed_bytes(n_rows, ld) + segs * 8 * seg_stride_of(ld);
+    Carver c(nullptr);
+    const SolveWs w = solve_layout(c, 0, n_rows, ld);
+    *bytes = (int64_t)c.bytes() + segs * 8 * w.seg_stride;
     return QREC_OK;
 }
 
@@ -369,13 +367,14 @@ extern "C" int qrec_als_solve_rows(const double *d_F, int64_t f_rows, const doub
     QREC_REQUIRE(lambda >= 0.0 && lambda <= 1.79769313486231570e308, "qrec_als_solve_rows: lambda must be finite and >= 0 (%g)", lambda);
     QREC_REQUIRE(d_G && d_X && d_indptr && d_ws && (d_F || f_rows == 0) && d_indices && d_c,
                  "qrec_als_solve_rows: null pointer");
-    QREC_REQUIRE(ws_bytes >= solve_fixed_bytes(n_rows, ld), "qrec_als_solve_rows: workspace of %lld bytes is too small", (long long)ws_bytes);
+    Carver c(d_ws);
+    const SolveWs w = solve_layout(c, ws_bytes, n_rows, ld);
+    QREC_REQUIRE(ws_bytes >= (int64_t)c.bytes(), "qrec_als_solve_rows: workspace of %lld bytes is too small", (long long)ws_bytes);
     if (n_rows == 0) {
         if (d_loss) QREC_HIP_CHECK(hipMemsetAsync(d_loss, 0, sizeof(double), as_stream(stream)));
         return QREC_OK;
     }
     hipStream_t st = as_stream(stream);
-    const SolveWs w = carve(d_ws, ws_bytes, n_rows, ld);
     const int with_loss = d_loss != nullptr;
     als_plan_kernel<<<1, 1024, 0, st>>>(d_indptr, n_rows, w);
     QREC_LAUNCH_CHECK();

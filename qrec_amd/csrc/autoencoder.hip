@@ -24,30 +24,8 @@ struct Ws {
     double *reg_part;    // [kRegBlocks]  partial sums of squares of the four weight variables
     float *dh_part;      // [B * kSplit][ld]
 };
-__host__ __device__ inline Ws carve(void *ws, int B, int ld) {
-    Ws w;
-    w.loss_part = static_cast<double *>(ws);
-    w.vsq = w.loss_part + (size_t)B * kSplit;
-    w.reg_part = w.vsq + B;
-    w.dh_part = reinterpret_cast<float *>(w.reg_part + kRegBlocks);
-    (void)ld;
-    return w;
-}
-
-__device__ inline float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// sum of a double over the workgroup in a fixed tree; every thread must call it, thread 0 receives the total
-__device__ inline double block_sum_fixed(double v, double *lds) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    int top = 1;
-    while (top < (int)blockDim.x) top <<= 1;          // blockDim need not be a power of two (ld = 96, 224, ...)
-    for (int s = top >> 1; s >= 1; s >>= 1) {
-        if (t < s && t + s < (int)blockDim.x) lds[t] += lds[t + s];
-        __syncthreads();
-    }
-    return lds[0];
+__host__ __device__ inline Ws ws_layout(Carver &c, int B, int ld) {
+    return {c.take<double>((size_t)B * kSplit), c.take<double>((size_t)B), c.take<double>(kRegBlocks), c.take<float>((size_t)B * kSplit * ld)};
 }
 
 // ---- encoder: one workgroup per batch row, one thread per hidden column ------------------------------------------------
@@ -228,7 +206,6 @@ __global__ __launch_bounds__(256) void loss_kernel(const double *__restrict__ lo
     for (int k = threadIdx.x; k < B; k += 256) r += vsq[k];
     r += reg_part[threadIdx.x];                      // kRegBlocks == the workgroup's size
     a = block_sum_fixed(a, red);
-    __syncthreads();
     r = block_sum_fixed(r, red);
     if (threadIdx.x == 0) out[0] = a * scale + reg * 0.5 * r;
 }
@@ -246,16 +223,6 @@ __global__ __launch_bounds__(256) void sigmoid_bias_kernel(float *__restrict__ S
 // choice(itemList), negatives a set), not its streams: every draw is Philox4x32-10 of (seed, step, position), so the lists
 // depend on nothing else.  Per batch row two bitmaps over the items (rated, sampled) make the negatives a set and give the
 // ascending order for free; the keep decision is evaluated only at the set bits.
-__device__ __forceinline__ void philox10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0], hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 constexpr uint32_t kTagUser = 0x75736572u, kTagNeg = 0x6e656761u, kTagKeep = 0x6b656570u;
 constexpr uint32_t kMaxDrawBlocks = 4096;          // a row whose user rated every item draws no negative (the reference would not return)
 
@@ -266,24 +233,13 @@ struct DrawWs {
     int32_t *in_pre;    // kept inputs of the row in the words before this one
     int32_t *lv_pre;    // live positions of the row in the words before this one
 };
-__host__ __device__ inline DrawWs carve_draw(void *ws, int B, int W) {
-    DrawWs d;
-    d.pos = static_cast<uint32_t *>(ws);
-    d.neg = d.pos + (size_t)B * W;
-    d.in_pre = reinterpret_cast<int32_t *>(d.neg + (size_t)B * W);
-    d.lv_pre = d.in_pre + (size_t)B * W;
-    return d;
+__host__ __device__ inline DrawWs draw_layout(Carver &c, int B, int W) {
+    const size_t n = (size_t)B * W;       // neg right behind pos: one memset clears both
+    return {c.take<uint32_t>(n), c.take<uint32_t>(n), c.take<int32_t>(n), c.take<int32_t>(n)};
 }
 
 // index of item in the ascending row, or -1
-__device__ inline int find_sorted(const int32_t *row, int len, int item) {
-    int lo = 0, hi = len;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (row[mid] < item) lo = mid + 1; else hi = mid;
-    }
-    return lo < len && row[lo] == item ? lo : -1;
-}
+__device__ inline int find_sorted(const int32_t *row, int len, int item) { return sorted_find(row, len, item); }
 
 // one workgroup per batch row: the user, the bits of its rated items, the bits of its per_rated * |rated| negatives.
 // The bitmaps are zero on entry; integer OR makes the result independent of the order the draws land in.
@@ -297,7 +253,7 @@ __global__ __launch_bounds__(256) void draw_row_kernel(const int64_t *__restrict
         int u = 0;
         for (uint32_t block = 0, done = 0; !done && block < kMaxDrawBlocks; block++) {
             uint32_t c[4] = {(uint32_t)b, 0u, block, step_lo};
-            philox10(c, seed_lo ^ kTagUser, seed_hi ^ step_hi);
+            philox4x32_10(c, seed_lo ^ kTagUser, seed_hi ^ step_hi);
             for (int w = 0; w < 4 && !done; w++) {
                 const uint32_t r = c[w] >> ushift;
                 if (r < (uint32_t)n_users) { u = (int)r; done = 1; }
@@ -321,7 +277,7 @@ __global__ __launch_bounds__(256) void draw_row_kernel(const int64_t *__restrict
     for (int64_t t = threadIdx.x; t < n_draws; t += 256) {
         for (uint32_t block = 0, done = 0; !done && block < kMaxDrawBlocks; block++) {
             uint32_t c[4] = {(uint32_t)t, (uint32_t)b, block, step_lo};
-            philox10(c, seed_lo ^ kTagNeg, seed_hi ^ step_hi);
+            philox4x32_10(c, seed_lo ^ kTagNeg, seed_hi ^ step_hi);
             for (int w = 0; w < 4 && !done; w++) {
                 const uint32_t r = c[w] >> ishift;
                 if (r >= (uint32_t)n_items || find_sorted(row, len, (int)r) >= 0) continue;
@@ -336,7 +292,7 @@ __global__ __launch_bounds__(256) void draw_row_kernel(const int64_t *__restrict
 __device__ inline bool keep_position(uint32_t item, uint32_t b, uint32_t seed_lo, uint32_t seed_hi, uint32_t step_lo, uint32_t step_hi,
                                      double keep_prob) {
     uint32_t c[4] = {item, b, step_lo, step_hi};
-    philox10(c, seed_lo ^ kTagKeep, seed_hi);
+    philox4x32_10(c, seed_lo ^ kTagKeep, seed_hi);
     return (double)c[0] * (1.0 / 4294967296.0) < keep_prob;
 }
 
@@ -505,7 +461,7 @@ extern "C" {
 
 int qrec_cdae_workspace_bytes(int32_t B, int32_t ld, int64_t *bytes) {
     QREC_REQUIRE(bytes && B >= 0 && ld >= 1, "qrec_cdae_workspace_bytes: bad arguments");
-    *bytes = (int64_t)sizeof(double) * ((int64_t)B * kSplit + B + kRegBlocks) + (int64_t)sizeof(float) * B * kSplit * ld;
+    *bytes = layout_bytes(ws_layout, B, ld);
     return QREC_OK;
 }
 
@@ -529,7 +485,7 @@ int qrec_cdae_decode(const float *d_Wdec, const float *d_bdec, int32_t n_items, 
     QREC_REQUIRE(B >= 0 && n_items >= 1, "qrec_cdae_decode: bad sizes");
     if (B == 0) return QREC_OK;
     QREC_REQUIRE(d_Wdec && d_bdec && d_h && d_lv_ptr && d_ws, "qrec_cdae_decode: null argument");
-    const Ws w = carve(d_ws, B, ld);
+    const Ws w = carve(d_ws, ws_layout, B, ld);
     const float scale = (float)(1.0 / ((double)B * (double)n_items));
     const dim3 grid((unsigned)B * kSplit);
 #define QREC_CDAE_DECODE(NK)                                                                                                       \
@@ -553,7 +509,7 @@ int qrec_cdae_hidden_bwd(const float *d_h, const float *d_V, int32_t n_users, in
     QREC_HIP_CHECK(hipMemsetAsync(d_gbenc, 0, sizeof(float) * (size_t)ld, st));
     if (B == 0) return QREC_OK;
     QREC_REQUIRE(d_h && d_V && d_users && d_ws && d_dz, "qrec_cdae_hidden_bwd: null argument");
-    const Ws w = carve(d_ws, B, ld);
+    const Ws w = carve(d_ws, ws_layout, B, ld);
     hipLaunchKernelGGL(hidden_bwd_kernel, dim3((unsigned)B), dim3((unsigned)ld), 0, st, d_h, w.dh_part, ld, d_dz);
     QREC_LAUNCH_CHECK();
     hipLaunchKernelGGL(user_grad_kernel, dim3((unsigned)B), dim3((unsigned)ld), 0, st, d_dz, d_V, n_users, nh, ld, d_users, B, reg, d_gV,
@@ -582,7 +538,7 @@ int qrec_cdae_weight_grads(const float *d_h, const float *d_dz, const float *d_g
 int qrec_cdae_loss(const float *d_theta, int64_t n_theta, float reg, int32_t B, int32_t n_items, int32_t ld, void *d_ws, double *d_loss,
                    void *stream) {
     QREC_REQUIRE(d_theta && n_theta >= 0 && B >= 1 && n_items >= 1 && ld >= 1 && d_ws && d_loss, "qrec_cdae_loss: bad arguments");
-    const Ws w = carve(d_ws, B, ld);
+    const Ws w = carve(d_ws, ws_layout, B, ld);
     hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(reg_part_kernel, dim3(kRegBlocks), dim3(256), 0, st, d_theta, n_theta, w.reg_part);
     QREC_LAUNCH_CHECK();
@@ -594,7 +550,7 @@ int qrec_cdae_loss(const float *d_theta, int64_t n_theta, float reg, int32_t B, 
 
 int qrec_cdae_draw_workspace_bytes(int32_t B, int32_t n_items, int64_t *bytes) {
     QREC_REQUIRE(bytes && B >= 0 && n_items >= 1, "qrec_cdae_draw_workspace_bytes: bad arguments");
-    *bytes = (int64_t)sizeof(uint32_t) * 4 * B * ((n_items + 31) / 32);
+    *bytes = layout_bytes(draw_layout, B, (n_items + 31) / 32);
     return QREC_OK;
 }
 
@@ -611,7 +567,7 @@ int qrec_cdae_draw_batch(const int64_t *d_rated_indptr, const int32_t *d_rated_i
                      d_in_crow && d_in_cval && d_lv_ptr && d_lv_item && d_lv_label && d_lv_cptr && d_lv_crow && d_lv_cslot,
                  "qrec_cdae_draw_batch: null argument");
     const int W = (n_items + 31) / 32;
-    const DrawWs w = carve_draw(d_ws, B, W);
+    const DrawWs w = carve(d_ws, draw_layout, B, W);
     hipStream_t st = as_stream(stream);
     const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32), step_lo = (uint32_t)step, step_hi = (uint32_t)(step >> 32);
     QREC_HIP_CHECK(hipMemsetAsync(w.pos, 0, sizeof(uint32_t) * 2 * (size_t)B * W, st));

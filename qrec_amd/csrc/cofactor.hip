@@ -38,8 +38,6 @@ constexpr int kTilePerWave = kTile / kWaves;
 enum Status { kOk = 0, kNotSpd = 1, kBadIndex = 3, kBadIndptr = 4 };
 enum Mode { kPre = 0, kSolo = 1, kLevel = 2 };
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
-
 __global__ void status_reset_kernel(int *status) {
     if (threadIdx.x == 0) { status[0] = kOk; status[1] = INT_MAX; }
 }
@@ -52,7 +50,12 @@ struct CoocArgs {
 };
 
 inline int64_t cooc_tiles(int64_t n_items) { return std::max<int64_t>(1, (n_items + kTile - 1) / kTile); }
-inline int64_t cooc_ws_bytes(int64_t n_items) { return 256 + align256(8 * (n_items * cooc_tiles(n_items) + 1)); }
+struct CoocWs { int *status; int64_t *offs; };      // offs [n_items * tiles + 1]: the kept pairs per (item, tile), then their scan
+CoocWs cooc_layout(Carver &c, int64_t n_items) {
+    const CoocWs w = {c.take<int>(2, 256), c.take<int64_t>((size_t)(n_items * cooc_tiles(n_items) + 1), 256)};
+    c.pad(256);
+    return w;
+}
 
 // The counters of tile [lo, hi) for item i into s_cnt; returns whether i has enough raters to keep any pair.
 __device__ inline bool cooc_tile(const CoocArgs &a, int64_t i, int64_t lo, int64_t hi, unsigned *s_cnt, int *status) {
@@ -158,13 +161,14 @@ __global__ __launch_bounds__(1024) void cooc_scan_kernel(int64_t *__restrict__ o
     for (int64_t r = lo; r < hi; ++r) { const int64_t v = offs[r]; offs[r] = run; run += v; }
 }
 
-int cooc_check(const char *who, const CoocArgs &a, const void *d_ws, int64_t ws_bytes) {
+int cooc_check(const char *who, const CoocArgs &a, void *d_ws, int64_t ws_bytes, CoocWs *w) {
     QREC_REQUIRE(a.n_items >= 1 && a.n_users >= 0 && a.i_nnz >= 0 && a.u_nnz >= 0 && a.n_items <= INT_MAX && a.n_users <= INT_MAX,
                  "%s: bad sizes (items %lld, users %lld)", who, (long long)a.n_items, (long long)a.n_users);
     QREC_REQUIRE(a.filter >= 0, "%s: filter must be >= 0 (%d)", who, a.filter);
     QREC_REQUIRE(a.i_indptr && a.u_indptr && (a.i_users || a.i_nnz == 0) && (a.u_items || a.u_nnz == 0) && d_ws, "%s: null pointer", who);
-    QREC_REQUIRE(ws_bytes >= cooc_ws_bytes(a.n_items), "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
-                 (long long)cooc_ws_bytes(a.n_items));
+    Carver c(d_ws);
+    *w = cooc_layout(c, a.n_items);
+    QREC_REQUIRE(ws_bytes >= (int64_t)c.bytes(), "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes, (long long)c.bytes());
     QREC_REQUIRE(a.n_items * a.n_tiles <= INT_MAX, "%s: too many (item, tile) blocks", who);
     return QREC_OK;
 }
@@ -375,8 +379,15 @@ __global__ __launch_bounds__(kThreads) void cofactor_commit_kernel(ItemArgs a, i
 
 bool valid_ld(int ld) { return ld == 16 || ld == 32 || ld == 64 || ld == 128; }
 
-inline int64_t item_ws_bytes(int64_t n_items, int64_t n_ctx, int ld) {
-    return 256 + 2 * align256(8 * n_items * ld) + 2 * align256(8 * n_items) + align256(8 * n_ctx * ((int64_t)ld * ld + ld));
+// the working copies and `pre` of ItemArgs
+void item_layout(Carver &c, int64_t n_items, int64_t n_ctx, int ld, ItemArgs *a) {
+    a->status = c.take<int>(2, 256);
+    a->Y = c.take<double>((size_t)(n_items * ld), 256);
+    a->G = c.take<double>((size_t)(n_items * ld), 256);
+    a->w = c.take<double>((size_t)n_items, 256);
+    a->c = c.take<double>((size_t)n_items, 256);
+    a->pre = c.take<double>((size_t)(n_ctx * ((int64_t)ld * ld + ld)), 256);
+    c.pad(256);
 }
 
 template <int T>
@@ -397,7 +408,7 @@ void launch_item_ld(int ld, const ItemArgs &a, int mode, const int32_t *list, in
 
 extern "C" int qrec_cooc_workspace_bytes(int64_t n_items, int64_t *bytes) {
     QREC_REQUIRE(bytes && n_items >= 1 && n_items <= INT_MAX, "qrec_cooc_workspace_bytes: bad arguments (n_items %lld)", (long long)n_items);
-    *bytes = cooc_ws_bytes(n_items);
+    *bytes = layout_bytes(cooc_layout, n_items);
     return QREC_OK;
 }
 
@@ -406,21 +417,20 @@ extern "C" int qrec_cooc_count(const int64_t *d_i_indptr, const int32_t *d_i_use
                                int64_t *kept, void *d_ws, int64_t ws_bytes, void *stream) {
     QREC_REQUIRE(kept, "qrec_cooc_count: null pointer");
     const CoocArgs a{d_i_indptr, d_i_users, n_items, i_nnz, d_u_indptr, d_u_items, n_users, u_nnz, filter, cooc_tiles(std::max<int64_t>(n_items, 1))};
-    if (int rc = cooc_check("qrec_cooc_count", a, d_ws, ws_bytes)) return rc;
+    CoocWs w;
+    if (int rc = cooc_check("qrec_cooc_count", a, d_ws, ws_bytes, &w)) return rc;
     hipStream_t st = as_stream(stream);
-    int *status = static_cast<int *>(d_ws);
-    int64_t *offs = reinterpret_cast<int64_t *>(static_cast<char *>(d_ws) + 256);
     const int64_t n = n_items * a.n_tiles;
-    status_reset_kernel<<<1, 64, 0, st>>>(status);
+    status_reset_kernel<<<1, 64, 0, st>>>(w.status);
     QREC_LAUNCH_CHECK();
-    cooc_kernel<false><<<(unsigned)n, kThreads, 0, st>>>(a, offs, status, nullptr, nullptr, nullptr, 0);
+    cooc_kernel<false><<<(unsigned)n, kThreads, 0, st>>>(a, w.offs, w.status, nullptr, nullptr, nullptr, 0);
     QREC_LAUNCH_CHECK();
-    cooc_scan_kernel<<<1, 1024, 0, st>>>(offs, n);
+    cooc_scan_kernel<<<1, 1024, 0, st>>>(w.offs, n);
     QREC_LAUNCH_CHECK();
     int h_status = 0;
     int64_t total = 0;
-    QREC_HIP_CHECK(hipMemcpyAsync(&h_status, status, sizeof(int), hipMemcpyDeviceToHost, st));
-    QREC_HIP_CHECK(hipMemcpyAsync(&total, offs + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    QREC_HIP_CHECK(hipMemcpyAsync(&h_status, w.status, sizeof(int), hipMemcpyDeviceToHost, st));
+    QREC_HIP_CHECK(hipMemcpyAsync(&total, w.offs + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     QREC_HIP_CHECK(hipStreamSynchronize(st));
     if (int rc = cooc_status("qrec_cooc_count", h_status)) return rc;
     *kept = total;
@@ -432,23 +442,22 @@ extern "C" int qrec_cooc_fill(const int64_t *d_i_indptr, const int32_t *d_i_user
                               int64_t *d_out_indptr, int32_t *d_out_cols, int32_t *d_out_counts, int64_t capacity, void *d_ws,
                               int64_t ws_bytes, void *stream) {
     const CoocArgs a{d_i_indptr, d_i_users, n_items, i_nnz, d_u_indptr, d_u_items, n_users, u_nnz, filter, cooc_tiles(std::max<int64_t>(n_items, 1))};
-    if (int rc = cooc_check("qrec_cooc_fill", a, d_ws, ws_bytes)) return rc;
+    CoocWs w;
+    if (int rc = cooc_check("qrec_cooc_fill", a, d_ws, ws_bytes, &w)) return rc;
     QREC_REQUIRE(d_out_indptr && capacity >= 0 && ((d_out_cols && d_out_counts) || capacity == 0), "qrec_cooc_fill: null pointer or capacity < 0");
     hipStream_t st = as_stream(stream);
-    int *status = static_cast<int *>(d_ws);
-    int64_t *offs = reinterpret_cast<int64_t *>(static_cast<char *>(d_ws) + 256);
     const int64_t n = n_items * a.n_tiles;
     int64_t total = 0;
-    QREC_HIP_CHECK(hipMemcpyAsync(&total, offs + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    QREC_HIP_CHECK(hipMemcpyAsync(&total, w.offs + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     QREC_HIP_CHECK(hipStreamSynchronize(st));
     QREC_REQUIRE(total >= 0 && total <= capacity, "qrec_cooc_fill: %lld kept pairs, room for %lld; nothing written (qrec_cooc_count of the same "
                  "inputs must come first)", (long long)total, (long long)capacity);
-    status_reset_kernel<<<1, 64, 0, st>>>(status);
+    status_reset_kernel<<<1, 64, 0, st>>>(w.status);
     QREC_LAUNCH_CHECK();
-    cooc_kernel<true><<<(unsigned)n, kThreads, 0, st>>>(a, offs, status, d_out_indptr, d_out_cols, d_out_counts, capacity);
+    cooc_kernel<true><<<(unsigned)n, kThreads, 0, st>>>(a, w.offs, w.status, d_out_indptr, d_out_cols, d_out_counts, capacity);
     QREC_LAUNCH_CHECK();
     int h_status = 0;
-    QREC_HIP_CHECK(hipMemcpyAsync(&h_status, status, sizeof(int), hipMemcpyDeviceToHost, st));
+    QREC_HIP_CHECK(hipMemcpyAsync(&h_status, w.status, sizeof(int), hipMemcpyDeviceToHost, st));
     QREC_HIP_CHECK(hipStreamSynchronize(st));
     return cooc_status("qrec_cooc_fill", h_status);
 }
@@ -457,7 +466,8 @@ extern "C" int qrec_cofactor_item_workspace_bytes(int64_t n_items, int64_t n_ctx
     QREC_REQUIRE(bytes && n_items >= 0 && n_ctx_items >= 0 && n_ctx_items <= n_items && valid_ld(ld),
                  "qrec_cofactor_item_workspace_bytes: bad arguments (n_items %lld, n_ctx_items %lld, ld %d)", (long long)n_items,
                  (long long)n_ctx_items, ld);
-    *bytes = item_ws_bytes(n_items, n_ctx_items, ld);
+    ItemArgs a{};
+    *bytes = layout_bytes(item_layout, n_items, n_ctx_items, ld, &a);
     return QREC_OK;
 }
 
@@ -485,18 +495,12 @@ extern "C" int qrec_cofactor_item_rows(const double *d_X, int64_t n_users, const
     }
     QREC_REQUIRE(n_ctx + n_solo <= n_items && (d_order || n_ctx == 0), "%s: %lld scheduled + %lld other items, %lld in the table", who,
                  (long long)n_ctx, (long long)n_solo, (long long)n_items);
-    QREC_REQUIRE(ws_bytes >= item_ws_bytes(n_items, n_ctx, ld), "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
-                 (long long)item_ws_bytes(n_items, n_ctx, ld));
+    ItemArgs a{};
+    Carver c(d_ws);
+    item_layout(c, n_items, n_ctx, ld, &a);
+    QREC_REQUIRE(ws_bytes >= (int64_t)c.bytes(), "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes, (long long)c.bytes());
     if (n_items == 0) return QREC_OK;
     hipStream_t st = as_stream(stream);
-    char *p = static_cast<char *>(d_ws);
-    ItemArgs a{};
-    a.status = reinterpret_cast<int *>(p); p += 256;
-    a.Y = reinterpret_cast<double *>(p); p += align256(8 * n_items * ld);
-    a.G = reinterpret_cast<double *>(p); p += align256(8 * n_items * ld);
-    a.w = reinterpret_cast<double *>(p); p += align256(8 * n_items);
-    a.c = reinterpret_cast<double *>(p); p += align256(8 * n_items);
-    a.pre = reinterpret_cast<double *>(p);
     a.X = d_X; a.n_users = n_users; a.XtX = d_XtX; a.n_items = n_items; a.d = d;
     a.r_indptr = d_r_indptr; a.r_users = d_r_users; a.r_conf = d_r_conf; a.r_nnz = r_nnz;
     a.s_indptr = d_s_indptr; a.s_items = d_s_items; a.s_vals = d_s_vals; a.s_nnz = s_nnz;

@@ -36,6 +36,30 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// ---- workspaces: a file states each layout ONCE, as a function (Carver &, shape...) that returns or fills the file's Ws
+// struct.  layout_bytes runs it on a null base for the *_bytes entry point, carve on the caller's buffer; an entry point that
+// is told the buffer's size runs it on a Carver of its own and checks the size against bytes() of that same walk.
+// Where a layout is a braced list of take() calls, the list is evaluated left to right: the arrays lie in the order of the fields.
+__host__ __device__ constexpr size_t align_up(size_t b, size_t a) { return (b + a - 1) & ~(a - 1); }   // a: a power of two
+struct Carver {
+    char *base; size_t off = 0;
+    __host__ __device__ explicit Carver(void *ws) : base(static_cast<char *>(ws)) {}
+    // the next `count` elements of T, starting at the next multiple of `align` bytes; null on a null base
+    template <typename T>
+    __host__ __device__ T *take(size_t count, size_t align = alignof(T)) {
+        pad(align);
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += count * sizeof(T);
+        return p;
+    }
+    __host__ __device__ void pad(size_t align) { off = align_up(off, align); }   // also: a layout that ends on a padded array
+    __host__ __device__ size_t bytes() const { return off; }
+};
+template <typename F, typename... A>
+int64_t layout_bytes(F layout, A... a) { Carver c(nullptr); layout(c, a...); return (int64_t)c.bytes(); }
+template <typename F, typename... A>
+auto carve(void *ws, F layout, A... a) { Carver c(ws); return layout(c, a...); }
+
 // ---- ordered scatter-add (ordered.hip): the deterministic counterpart of the float-atomic gradient scatters.  A producer
 // writes slot s's row to contrib[s][ld] and its destination row to keys[s] (< 0: none); ordered_scatter_run sorts (key, slot)
 // stably and adds each row's slots in ascending slot order, class by class (class = slot / class_size; 0: one class).
@@ -115,6 +139,54 @@ __device__ inline T wave_sum_dpp(T v) {
     t = t + dpp_take<0x142, 0xa, 0xf>(t);            // row_bcast:15 into rows 1 and 3
     t = t + dpp_take<0x143, 0xc, 0xf>(t);            // row_bcast:31 into rows 2 and 3 -> lane 63 holds the total
     return read_lane63(t);
+}
+
+// ---- device helpers more than one kernel file needs; each exists once, here
+// Philox4x32-10 (Salmon et al., SC'11): c = the four counter words in and the four random words out, (k0, k1) the key.  Every
+// device stream of the library is this function of a counter and key its caller builds; oracle/c.py::philox4x32_10 and
+// tests/device_stream.py restate it bit for bit.
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0], hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+// the uniform in [0, 1) of a random word's top 24 bits: exact in fp32
+__device__ inline float uniform24(uint32_t w) { return (float)(w >> 8) * 0x1p-24f; }
+
+__device__ inline float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// Sum of a double over the workgroup (any size; lds holds blockDim.x doubles) in one fixed tree, so the bits do not depend on
+// the launch.  Every thread calls it, every thread receives the total, and back-to-back calls on one lds array are safe: the
+// leading barrier keeps a call from overwriting lds[0] while a thread still reads the previous call's total from it.
+__device__ inline double block_sum_fixed(double v, double *lds) {
+    const int t = threadIdx.x, n = (int)blockDim.x;
+    __syncthreads();
+    lds[t] = v;
+    __syncthreads();
+    int top = 1;
+    while (top < n) top <<= 1;                        // blockDim need not be a power of two
+    for (int s = top >> 1; s >= 1; s >>= 1) {
+        if (t < s && t + s < n) lds[t] += lds[t + s];
+        __syncthreads();
+    }
+    return lds[0];
+}
+
+// index of item in the ascending row[0, len), or -1
+template <typename Len>
+__device__ inline Len sorted_find(const int32_t *__restrict__ row, Len len, int item) {
+    Len lo = 0, hi = len;
+    while (lo < hi) {
+        const Len mid = (lo + hi) >> 1;
+        if (row[mid] < item) lo = mid + 1; else hi = mid;
+    }
+    return lo < len && row[lo] == item ? lo : -1;
 }
 
 }  // namespace qrec

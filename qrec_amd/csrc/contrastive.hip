@@ -18,19 +18,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// ---- Philox4x32-10 (same generator as the negative sampler) ---------------------------------
-__device__ __forceinline__ void philox10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-        const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-        const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
 // One group of LPR lanes per row, float4 per lane (ld = 4*LPR).  V views are formed from the same source row in one pass.
 //   noise[v] != nullptr : use the given U[0,1) numbers (parity tests inject TF-side noise).  An injected value may also carry the SIGN
 //                         the perturbation is to use instead of sign(emb) -- sign() is discontinuous, and a test that follows a
@@ -76,9 +63,9 @@ __global__ __launch_bounds__(256) void perturb_kernel(PerturbViews pv, const flo
                 const uint64_t sid = pv.stream_id[v];
                 const int64_t grow = row + philox_row0;      // the table row this block row stands for (row-partitioned tables)
                 uint32_t c[4] = {(uint32_t)grow, (uint32_t)(grow >> 32) ^ ((uint32_t)r << 8), (uint32_t)sid, (uint32_t)(sid >> 32)};
-                philox10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-                nz.x = (float)(c[0] >> 8) * 0x1p-24f; nz.y = (float)(c[1] >> 8) * 0x1p-24f;
-                nz.z = (float)(c[2] >> 8) * 0x1p-24f; nz.w = (float)(c[3] >> 8) * 0x1p-24f;
+                philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+                nz.x = uniform24(c[0]); nz.y = uniform24(c[1]);
+                nz.z = uniform24(c[2]); nz.w = uniform24(c[3]);
             }
             if (4 * r + 0 >= d) nz.x = 0.f;
             if (4 * r + 1 >= d) nz.y = 0.f;
@@ -317,32 +304,47 @@ __global__ __launch_bounds__(256) void normalize_bwd_kernel(const float *__restr
     *reinterpret_cast<f32x4 *>(d_out + dst) = o;
 }
 
+// packed floats; n is padded to a multiple of 64 rows
+struct InfoNceWs {
+    float *z1, *z2;                   // [n_pad][ld] the normalised rows of the two views
+    float *dz1, *dz2;                 // [kSplitK][n_pad][ld] their gradients, one part per K slice
+    float *r1, *r2, *dotp, *inv_ttl;  // [n_pad] each
+    float *psum;                      // [n_pad/32][n_pad]
+    float *ExT, *Ex;                  // [n_pad][n_pad], the two orientations
+};
+InfoNceWs info_nce_layout(Carver &c, int64_t n, int64_t ld) {
+    const size_t n_pad = (size_t)((n + 63) / 64 * 64), tab = n_pad * (size_t)ld;
+    InfoNceWs w;
+    w.z1 = c.take<float>(tab); w.z2 = c.take<float>(tab);
+    w.dz1 = c.take<float>(kSplitK * tab); w.dz2 = c.take<float>(kSplitK * tab);
+    w.r1 = c.take<float>(n_pad); w.r2 = c.take<float>(n_pad); w.dotp = c.take<float>(n_pad); w.inv_ttl = c.take<float>(n_pad);
+    w.psum = c.take<float>(n_pad / 32 * n_pad);
+    w.ExT = c.take<float>(n_pad * n_pad); w.Ex = c.take<float>(n_pad * n_pad);
+    return w;
+}
+
 template <int LPR>
 int run_info_nce(const float *S1, const float *S2, float div, const int32_t *rows, int n, int ld, float tau,
-                 float cl_rate, float *ws, float *d_out, float *d_out2, double *loss, hipStream_t st) {
+                 float cl_rate, void *ws, float *d_out, float *d_out2, double *loss, hipStream_t st) {
     constexpr int GPW = kWave / LPR;
     const int n_pad = (n + 63) / 64 * 64;
     const int64_t tab = (int64_t)n_pad * ld;
-    float *z1 = ws, *z2 = z1 + tab, *dz1 = z2 + tab, *dz2 = dz1 + kSplitK * tab;
-    float *r1 = dz2 + kSplitK * tab, *r2 = r1 + n_pad, *dotp = r2 + n_pad, *inv_ttl = dotp + n_pad;
-    float *psum = inv_ttl + n_pad;                       // [n_pad/32][n_pad]
-    float *ExT = psum + (int64_t)(n_pad / 32) * n_pad;   // [n_pad][n_pad]
-    float *Ex = ExT + (int64_t)n_pad * n_pad;            // [n_pad][n_pad], the other orientation
+    const InfoNceWs w = carve(ws, info_nce_layout, n, ld);
     const float inv_tau = 1.0f / tau;
     const unsigned row_blocks = (unsigned)((n + 4 * GPW - 1) / (4 * GPW)), pad_blocks = (unsigned)((n_pad + 4 * GPW - 1) / (4 * GPW));
-    hipLaunchKernelGGL((gather_normalize_kernel<LPR>), dim3(pad_blocks), dim3(256), 0, st, S1, S2, div, rows, n, n_pad, z1, z2, r1, r2, dotp);
+    hipLaunchKernelGGL((gather_normalize_kernel<LPR>), dim3(pad_blocks), dim3(256), 0, st, S1, S2, div, rows, n, n_pad, w.z1, w.z2, w.r1, w.r2, w.dotp);
     QREC_LAUNCH_CHECK();
     hipLaunchKernelGGL(exp_logits_kernel, dim3((unsigned)(n_pad / 32), (unsigned)((n_pad / 32 + 3) / 4)), dim3(256), 0, st,
-                       z1, z2, n, n_pad, ld, inv_tau, ExT, Ex, psum);
+                       w.z1, w.z2, n, n_pad, ld, inv_tau, w.ExT, w.Ex, w.psum);
     QREC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, st, psum, n_pad / 32, n, n_pad, dotp, inv_tau, inv_ttl, loss);
+    hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, st, w.psum, n_pad / 32, n, n_pad, w.dotp, inv_tau, w.inv_ttl, loss);
     QREC_LAUNCH_CHECK();
     const dim3 gg((unsigned)(n_pad / 32), (unsigned)((ld + 31) / 32), (unsigned)(kSplitK / 4));
-    hipLaunchKernelGGL((grad_z_kernel<0>), gg, dim3(256), 0, st, Ex, inv_ttl, z2, n, n_pad, ld, inv_tau, 1.f, dz1);
+    hipLaunchKernelGGL((grad_z_kernel<0>), gg, dim3(256), 0, st, w.Ex, w.inv_ttl, w.z2, n, n_pad, ld, inv_tau, 1.f, w.dz1);
     QREC_LAUNCH_CHECK();
-    hipLaunchKernelGGL((grad_z_kernel<1>), gg, dim3(256), 0, st, ExT, inv_ttl, z1, n, n_pad, ld, inv_tau, 1.f, dz2);
+    hipLaunchKernelGGL((grad_z_kernel<1>), gg, dim3(256), 0, st, w.ExT, w.inv_ttl, w.z1, n, n_pad, ld, inv_tau, 1.f, w.dz2);
     QREC_LAUNCH_CHECK();
-    hipLaunchKernelGGL((normalize_bwd_kernel<LPR>), dim3(row_blocks), dim3(256), 0, st, z1, z2, dz1, dz2, r1, r2, rows, n, tab, cl_rate, d_out, d_out2);
+    hipLaunchKernelGGL((normalize_bwd_kernel<LPR>), dim3(row_blocks), dim3(256), 0, st, w.z1, w.z2, w.dz1, w.dz2, w.r1, w.r2, rows, n, tab, cl_rate, d_out, d_out2);
     QREC_LAUNCH_CHECK();
     return QREC_OK;
 }
@@ -498,61 +500,63 @@ __global__ __launch_bounds__(256) void sept_normalize_bwd_kernel(const float *__
     *reinterpret_cast<f32x4 *>(d_out + dst) = o;
 }
 
-inline int64_t sept_ws_floats(int64_t n, int64_t ld, int64_t k) {
-    const int64_t n_pad = (n + 63) / 64 * 64, tab = n_pad * ld;
-    // z x4, dzc, dac, dz parts (1 set), da parts (3 sets), r x4 + dotp scratch, ttl1 x3, ttl, inv_ttl, inv_pos, psum, Ex1 x3, Ex, ExT, labels
-    return 6 * tab + 4 * kSplitK * tab + 11 * n_pad + (n_pad / 32) * n_pad + 5 * n_pad * n_pad + 3 * n_pad * k;
+// packed floats, then the labels; n is padded to a multiple of 64 rows
+struct SeptWs {
+    float *z[4];                      // [n_pad][ld] the normalised rows of the four views
+    float *dzc, *dac;                 // [n_pad][ld] the positives' part of the gradient
+    float *dzp, *dap;                 // [kSplitK][n_pad][ld], [3][kSplitK][n_pad][ld] the split-K parts
+    float *rinv[4], *dotp, *ttl1[3], *ttl, *inv_ttl, *inv_pos;   // [n_pad] each
+    float *psum;                      // [n_pad/32][n_pad]
+    float *Ex1[3], *Ex, *ExT;         // [n_pad][n_pad] each
+    int32_t *labels;                  // [3][n][k], sized as [3][n_pad][k]
+};
+SeptWs sept_layout(Carver &c, int64_t n, int64_t ld, int64_t k) {
+    const size_t n_pad = (size_t)((n + 63) / 64 * 64), tab = n_pad * (size_t)ld, sq = n_pad * n_pad;
+    SeptWs w;
+    for (int v = 0; v < 4; v++) w.z[v] = c.take<float>(tab);
+    w.dzc = c.take<float>(tab); w.dac = c.take<float>(tab);
+    w.dzp = c.take<float>(kSplitK * tab); w.dap = c.take<float>(3 * kSplitK * tab);
+    for (int v = 0; v < 4; v++) w.rinv[v] = c.take<float>(n_pad);
+    w.dotp = c.take<float>(n_pad);
+    for (int v = 0; v < 3; v++) w.ttl1[v] = c.take<float>(n_pad);
+    w.ttl = c.take<float>(n_pad); w.inv_ttl = c.take<float>(n_pad); w.inv_pos = c.take<float>(n_pad);
+    w.psum = c.take<float>(n_pad / 32 * n_pad);
+    for (int v = 0; v < 3; v++) w.Ex1[v] = c.take<float>(sq);
+    w.Ex = c.take<float>(sq); w.ExT = c.take<float>(sq);
+    w.labels = c.take<int32_t>(3 * n_pad * (size_t)k);
+    return w;
 }
 
 template <int LPR>
-int run_sept_ssl(const float *const S[4], const int32_t *rows, int n, int ld, int k, float ss_rate, float *ws,
+int run_sept_ssl(const float *const S[4], const int32_t *rows, int n, int ld, int k, float ss_rate, void *ws,
                  float *const dS[4], double *loss, int32_t *labels_out, const OrderedScatterWs *ow, hipStream_t st) {
     constexpr int GPW = kWave / LPR;
     const int n_pad = (n + 63) / 64 * 64;
-    const int64_t tab = (int64_t)n_pad * ld, sq = (int64_t)n_pad * n_pad;
-    float *z[4]; float *p = ws;
-    for (int v = 0; v < 4; v++) { z[v] = p; p += tab; }
-    float *dzc = p; p += tab;
-    float *dac = p; p += tab;
-    float *dzp = p; p += kSplitK * tab;
-    float *dap = p; p += 3 * kSplitK * tab;
-    float *rinv[4];
-    for (int v = 0; v < 4; v++) { rinv[v] = p; p += n_pad; }
-    float *dotp = p; p += n_pad;
-    float *ttl1[3];
-    for (int v = 0; v < 3; v++) { ttl1[v] = p; p += n_pad; }
-    float *ttl = p; p += n_pad;
-    float *inv_ttl = p; p += n_pad;
-    float *inv_pos = p; p += n_pad;
-    float *psum = p; p += (int64_t)(n_pad / 32) * n_pad;
-    float *Ex1[3];
-    for (int v = 0; v < 3; v++) { Ex1[v] = p; p += sq; }
-    float *Ex = p; p += sq;
-    float *ExT = p; p += sq;
-    int32_t *labels = reinterpret_cast<int32_t *>(p);                       // [3][n][k]
+    const int64_t tab = (int64_t)n_pad * ld;
+    const SeptWs w = carve(ws, sept_layout, n, ld, k);
     const float inv_tau = 10.0f;                                            // tau = 0.1, SEPT.py:245-246
     const unsigned row_blocks = (unsigned)((n + 4 * GPW - 1) / (4 * GPW)), pad_blocks = (unsigned)((n_pad + 4 * GPW - 1) / (4 * GPW));
     const dim3 eg((unsigned)(n_pad / 32), (unsigned)((n_pad / 32 + 3) / 4));
     const dim3 gg((unsigned)(n_pad / 32), (unsigned)((ld + 31) / 32), (unsigned)(kSplitK / 4));
     const unsigned stat_blocks = (unsigned)((n_pad * 8 + 255) / 256);
     // z_f, z_h | z_e, a   (S[0] friend, S[1] sharing, S[2] preference, S[3] augmented view)
-    hipLaunchKernelGGL((gather_normalize_kernel<LPR>), dim3(pad_blocks), dim3(256), 0, st, S[0], S[1], 1.0f, rows, n, n_pad, z[0], z[1], rinv[0], rinv[1], dotp);
+    hipLaunchKernelGGL((gather_normalize_kernel<LPR>), dim3(pad_blocks), dim3(256), 0, st, S[0], S[1], 1.0f, rows, n, n_pad, w.z[0], w.z[1], w.rinv[0], w.rinv[1], w.dotp);
     QREC_LAUNCH_CHECK();
-    hipLaunchKernelGGL((gather_normalize_kernel<LPR>), dim3(pad_blocks), dim3(256), 0, st, S[2], S[3], 1.0f, rows, n, n_pad, z[2], z[3], rinv[2], rinv[3], dotp);
+    hipLaunchKernelGGL((gather_normalize_kernel<LPR>), dim3(pad_blocks), dim3(256), 0, st, S[2], S[3], 1.0f, rows, n, n_pad, w.z[2], w.z[3], w.rinv[2], w.rinv[3], w.dotp);
     QREC_LAUNCH_CHECK();
     // label_prediction (SEPT.py:214-224): softmax rows of z_v a^T -> exp and row totals, tau = 1
     for (int v = 0; v < 3; v++) {
-        hipLaunchKernelGGL(exp_logits_kernel, eg, dim3(256), 0, st, z[v], z[3], n, n_pad, ld, 1.0f, ExT, Ex1[v], psum);
+        hipLaunchKernelGGL(exp_logits_kernel, eg, dim3(256), 0, st, w.z[v], w.z[3], n, n_pad, ld, 1.0f, w.ExT, w.Ex1[v], w.psum);
         QREC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(row_total_kernel, dim3(stat_blocks), dim3(256), 0, st, psum, n, n_pad, ttl1[v], (float *)nullptr);
+        hipLaunchKernelGGL(row_total_kernel, dim3(stat_blocks), dim3(256), 0, st, w.psum, n, n_pad, w.ttl1[v], (float *)nullptr);
         QREC_LAUNCH_CHECK();
     }
     // pseudo labels of encoder v = top-k of the OTHER two encoders' averaged predictions (SEPT.py:258-260)
     const int other[3][2] = {{1, 2}, {0, 2}, {0, 1}};
     for (int v = 0; v < 3; v++) {
 #define QREC_TOPK(EPL)                                                                                                        \
-    hipLaunchKernelGGL((topk_pair_kernel<EPL>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, Ex1[other[v][0]], ttl1[other[v][0]], \
-                       Ex1[other[v][1]], ttl1[other[v][1]], n, n_pad, k, labels + (int64_t)v * n * k)
+    hipLaunchKernelGGL((topk_pair_kernel<EPL>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, w.Ex1[other[v][0]], w.ttl1[other[v][0]], \
+                       w.Ex1[other[v][1]], w.ttl1[other[v][1]], n, n_pad, k, w.labels + (int64_t)v * n * k)
         if (n_pad <= 512) QREC_TOPK(8);
         else if (n_pad <= 1024) QREC_TOPK(16);
         else if (n_pad <= 2048) QREC_TOPK(32);
@@ -561,32 +565,32 @@ int run_sept_ssl(const float *const S[4], const int32_t *rows, int n, int ld, in
 #undef QREC_TOPK
         QREC_LAUNCH_CHECK();
     }
-    if (labels_out) QREC_HIP_CHECK(hipMemcpyAsync(labels_out, labels, sizeof(int32_t) * 3 * (size_t)n * k, hipMemcpyDeviceToDevice, st));
-    QREC_HIP_CHECK(hipMemsetAsync(dac, 0, sizeof(float) * tab, st));
+    if (labels_out) QREC_HIP_CHECK(hipMemcpyAsync(labels_out, w.labels, sizeof(int32_t) * 3 * (size_t)n * k, hipMemcpyDeviceToDevice, st));
+    QREC_HIP_CHECK(hipMemsetAsync(w.dac, 0, sizeof(float) * tab, st));
     // neighbor_discrimination per encoder (SEPT.py:233-248), tau = 0.1
     for (int v = 0; v < 3; v++) {
-        const int32_t *lab = labels + (int64_t)v * n * k;
-        hipLaunchKernelGGL(exp_logits_kernel, eg, dim3(256), 0, st, z[v], z[3], n, n_pad, ld, inv_tau, ExT, Ex, psum);
+        const int32_t *lab = w.labels + (int64_t)v * n * k;
+        hipLaunchKernelGGL(exp_logits_kernel, eg, dim3(256), 0, st, w.z[v], w.z[3], n, n_pad, ld, inv_tau, w.ExT, w.Ex, w.psum);
         QREC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(row_total_kernel, dim3(stat_blocks), dim3(256), 0, st, psum, n, n_pad, ttl, inv_ttl);
+        hipLaunchKernelGGL(row_total_kernel, dim3(stat_blocks), dim3(256), 0, st, w.psum, n, n_pad, w.ttl, w.inv_ttl);
         QREC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sept_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Ex, ttl, lab, n, n_pad, k, inv_pos, loss);
+        hipLaunchKernelGGL(sept_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w.Ex, w.ttl, lab, n, n_pad, k, w.inv_pos, loss);
         QREC_LAUNCH_CHECK();
-        hipLaunchKernelGGL((grad_z_kernel<0>), gg, dim3(256), 0, st, Ex, inv_ttl, z[3], n, n_pad, ld, inv_tau, 0.f, dzp);
+        hipLaunchKernelGGL((grad_z_kernel<0>), gg, dim3(256), 0, st, w.Ex, w.inv_ttl, w.z[3], n, n_pad, ld, inv_tau, 0.f, w.dzp);
         QREC_LAUNCH_CHECK();
-        hipLaunchKernelGGL((grad_z_kernel<1>), gg, dim3(256), 0, st, ExT, inv_ttl, z[v], n, n_pad, ld, inv_tau, 0.f, dap + (int64_t)v * kSplitK * tab);
+        hipLaunchKernelGGL((grad_z_kernel<1>), gg, dim3(256), 0, st, w.ExT, w.inv_ttl, w.z[v], n, n_pad, ld, inv_tau, 0.f, w.dap + (int64_t)v * kSplitK * tab);
         QREC_LAUNCH_CHECK();
-        hipLaunchKernelGGL((sept_sparse_kernel<LPR>), dim3(row_blocks), dim3(256), 0, st, Ex, inv_pos, lab, z[v], z[3], n, n_pad, k, inv_tau, dzc, dac,
+        hipLaunchKernelGGL((sept_sparse_kernel<LPR>), dim3(row_blocks), dim3(256), 0, st, w.Ex, w.inv_pos, lab, w.z[v], w.z[3], n, n_pad, k, inv_tau, w.dzc, w.dac,
                            ow ? ow->contrib : (float *)nullptr, ow ? ow->keys : (int32_t *)nullptr);
         QREC_LAUNCH_CHECK();
         if (ow) {
-            const int rc = ordered_scatter_run(*ow, (int64_t)n * k, ld, 0, dac, st);
+            const int rc = ordered_scatter_run(*ow, (int64_t)n * k, ld, 0, w.dac, st);
             if (rc != QREC_OK) return rc;
         }
-        hipLaunchKernelGGL((sept_normalize_bwd_kernel<LPR>), dim3(row_blocks), dim3(256), 0, st, z[v], dzp, kSplitK, tab, dzc, rinv[v], rows, n, ss_rate, dS[v]);
+        hipLaunchKernelGGL((sept_normalize_bwd_kernel<LPR>), dim3(row_blocks), dim3(256), 0, st, w.z[v], w.dzp, kSplitK, tab, w.dzc, w.rinv[v], rows, n, ss_rate, dS[v]);
         QREC_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL((sept_normalize_bwd_kernel<LPR>), dim3(row_blocks), dim3(256), 0, st, z[3], dap, 3 * kSplitK, tab, dac, rinv[3], rows, n, ss_rate, dS[3]);
+    hipLaunchKernelGGL((sept_normalize_bwd_kernel<LPR>), dim3(row_blocks), dim3(256), 0, st, w.z[3], w.dap, 3 * kSplitK, tab, w.dac, w.rinv[3], rows, n, ss_rate, dS[3]);
     QREC_LAUNCH_CHECK();
     return QREC_OK;
 }
@@ -641,8 +645,7 @@ int qrec_perturb_two_views(const float *d_src, float *d_emb1, float *d_emb2, int
 
 int qrec_info_nce_workspace_bytes(int32_t n, int32_t ld, int64_t *bytes) {
     QREC_REQUIRE(bytes && n >= 0 && ld > 0, "qrec_info_nce_workspace_bytes: bad argument");
-    const int64_t n_pad = ((int64_t)n + 63) / 64 * 64;
-    *bytes = 4 * ((2 + 2 * 16) * n_pad * ld + 4 * n_pad + (n_pad / 32) * n_pad + 2 * n_pad * n_pad);
+    *bytes = layout_bytes(info_nce_layout, n, ld);
     return QREC_OK;
 }
 
@@ -655,19 +658,18 @@ int qrec_info_nce_loss_grad(const float *d_S1, const float *d_S2, float div, con
     QREC_REQUIRE(n <= 16384, "qrec_info_nce_loss_grad: at most 16384 unique rows per call");
     if (n == 0) return QREC_OK;
     hipStream_t st = as_stream(stream);
-    float *ws = static_cast<float *>(d_workspace);
     switch (ld) {
-        case 32: return run_info_nce<8>(d_S1, d_S2, div, d_rows, n, ld, tau, cl_rate, ws, d_out, d_out2, d_loss, st);
-        case 64: return run_info_nce<16>(d_S1, d_S2, div, d_rows, n, ld, tau, cl_rate, ws, d_out, d_out2, d_loss, st);
-        case 128: return run_info_nce<32>(d_S1, d_S2, div, d_rows, n, ld, tau, cl_rate, ws, d_out, d_out2, d_loss, st);
-        case 256: return run_info_nce<64>(d_S1, d_S2, div, d_rows, n, ld, tau, cl_rate, ws, d_out, d_out2, d_loss, st);
+        case 32: return run_info_nce<8>(d_S1, d_S2, div, d_rows, n, ld, tau, cl_rate, d_workspace, d_out, d_out2, d_loss, st);
+        case 64: return run_info_nce<16>(d_S1, d_S2, div, d_rows, n, ld, tau, cl_rate, d_workspace, d_out, d_out2, d_loss, st);
+        case 128: return run_info_nce<32>(d_S1, d_S2, div, d_rows, n, ld, tau, cl_rate, d_workspace, d_out, d_out2, d_loss, st);
+        case 256: return run_info_nce<64>(d_S1, d_S2, div, d_rows, n, ld, tau, cl_rate, d_workspace, d_out, d_out2, d_loss, st);
         default: set_error("qrec_info_nce_loss_grad: row stride must be 32, 64, 128 or 256 floats (got %d)", ld); return QREC_ERR_INVALID;
     }
 }
 
 int qrec_sept_ssl_workspace_bytes(int32_t n, int32_t ld, int32_t k, int64_t *bytes) {
     QREC_REQUIRE(bytes && n >= 0 && ld > 0 && k >= 1, "qrec_sept_ssl_workspace_bytes: bad argument");
-    *bytes = 4 * sept_ws_floats(n, ld, k);
+    *bytes = layout_bytes(sept_layout, n, ld, k);
     return QREC_OK;
 }
 
@@ -682,7 +684,6 @@ int qrec_sept_ssl_loss_grad(const float *d_S_friend, const float *d_S_sharing, c
     if (n == 0) return QREC_OK;
     QREC_REQUIRE(k >= 1 && k <= n, "qrec_sept_ssl_loss_grad: need 1 <= ins_cnt <= unique users in the batch (got %d, %d)", k, n);
     hipStream_t st = as_stream(stream);
-    float *ws = static_cast<float *>(d_workspace);
     const float *const S[4] = {d_S_friend, d_S_sharing, d_S_pref, d_S_aug};
     float *const dS[4] = {d_dS_friend, d_dS_sharing, d_dS_pref, d_dS_aug};
     OrderedScatterWs ow = {};
@@ -693,10 +694,10 @@ int qrec_sept_ssl_loss_grad(const float *d_S_friend, const float *d_S_sharing, c
     }
     const OrderedScatterWs *owp = d_ordered_ws ? &ow : nullptr;
     switch (ld) {
-        case 32: return run_sept_ssl<8>(S, d_rows, n, ld, k, ss_rate, ws, dS, d_loss, d_labels, owp, st);
-        case 64: return run_sept_ssl<16>(S, d_rows, n, ld, k, ss_rate, ws, dS, d_loss, d_labels, owp, st);
-        case 128: return run_sept_ssl<32>(S, d_rows, n, ld, k, ss_rate, ws, dS, d_loss, d_labels, owp, st);
-        case 256: return run_sept_ssl<64>(S, d_rows, n, ld, k, ss_rate, ws, dS, d_loss, d_labels, owp, st);
+        case 32: return run_sept_ssl<8>(S, d_rows, n, ld, k, ss_rate, d_workspace, dS, d_loss, d_labels, owp, st);
+        case 64: return run_sept_ssl<16>(S, d_rows, n, ld, k, ss_rate, d_workspace, dS, d_loss, d_labels, owp, st);
+        case 128: return run_sept_ssl<32>(S, d_rows, n, ld, k, ss_rate, d_workspace, dS, d_loss, d_labels, owp, st);
+        case 256: return run_sept_ssl<64>(S, d_rows, n, ld, k, ss_rate, d_workspace, dS, d_loss, d_labels, owp, st);
         default: set_error("qrec_sept_ssl_loss_grad: row stride must be 32, 64, 128 or 256 floats (got %d)", ld); return QREC_ERR_INVALID;
     }
 }

@@ -62,15 +62,22 @@ struct SolveWs {
     int *status;         // [0] Status of the call, [1] smallest row whose pivot failed, [2] Status of the checks (fixed before the solve)
     double *x_new;       // [n_rows][ld]
 };
+SolveWs solve_layout(Carver &c, int64_t n_rows, int ld) {
+    const SolveWs w = {c.take<int>(4, 256), c.take<double>((size_t)(n_rows * ld), 256)};
+    c.pad(256);
+    return w;
+}
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
-inline int64_t solve_ws_bytes(int64_t n_rows, int ld) { return align256(16) + align256(8 * n_rows * ld); }
-
-SolveWs carve_solve(void *ws) {
-    char *p = static_cast<char *>(ws);
-    SolveWs w;
-    w.status = reinterpret_cast<int *>(p); p += align256(16);
-    w.x_new = reinterpret_cast<double *>(p);
+// status as in SolveWs; partial [n_seg][n_cols], one row per kPriorSegment users; a_new and mu_new [n_cols]
+struct PriorWs { int *status; double *partial, *a_new, *mu_new; int n_seg; };
+PriorWs prior_layout(Carver &c, int64_t n_rows, int64_t n_cols) {
+    PriorWs w;
+    w.n_seg = (int)std::max<int64_t>(1, (n_rows + kPriorSegment - 1) / kPriorSegment);
+    w.status = c.take<int>(4, 256);
+    w.partial = c.take<double>((size_t)(w.n_seg * n_cols), 256);
+    w.a_new = c.take<double>((size_t)n_cols, 256);
+    w.mu_new = c.take<double>((size_t)n_cols, 256);
+    c.pad(256);
     return w;
 }
 
@@ -333,7 +340,7 @@ void launch_solve(const double *F, int64_t n_cols, const double *X, int64_t n_ro
 extern "C" int qrec_expo_solve_workspace_bytes(int64_t n_rows, int32_t ld, int64_t *bytes) {
     QREC_REQUIRE(bytes && n_rows >= 0 && valid_ld(ld), "qrec_expo_solve_workspace_bytes: bad arguments (n_rows %lld, ld %d)",
                  (long long)n_rows, ld);
-    *bytes = solve_ws_bytes(n_rows, ld);
+    *bytes = layout_bytes(solve_layout, n_rows, ld);
     return QREC_OK;
 }
 
@@ -348,12 +355,13 @@ extern "C" int qrec_expo_solve_rows(const double *d_F, int64_t n_cols, double *d
     QREC_REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < INT_MAX, "qrec_expo_solve_rows: bad row counts");
     QREC_REQUIRE(lambda >= 0.0 && std::isfinite(lambda), "qrec_expo_solve_rows: lambda must be finite and >= 0 (%g)", lambda);
     QREC_REQUIRE(d_X && d_indptr && d_indices && d_ws && (d_F || n_cols == 0), "qrec_expo_solve_rows: null pointer");
-    QREC_REQUIRE(ws_bytes >= solve_ws_bytes(n_rows, ld), "qrec_expo_solve_rows: workspace of %lld bytes is too small", (long long)ws_bytes);
+    Carver c(d_ws);
+    const SolveWs w = solve_layout(c, n_rows, ld);
+    QREC_REQUIRE(ws_bytes >= (int64_t)c.bytes(), "qrec_expo_solve_rows: workspace of %lld bytes is too small", (long long)ws_bytes);
     Prior pr;
     if (int e = to_prior(prior, "qrec_expo_solve_rows", &pr)) return e;
     if (n_rows == 0) return QREC_OK;
     hipStream_t st = as_stream(stream);
-    const SolveWs w = carve_solve(d_ws);
     expo_check_kernel<<<1, kThreads, 0, st>>>(d_indptr, n_rows, w.status);
     QREC_LAUNCH_CHECK();
     switch (ld) {
@@ -385,8 +393,7 @@ extern "C" int qrec_expo_solve_rows(const double *d_F, int64_t n_cols, double *d
 
 extern "C" int qrec_expo_prior_workspace_bytes(int64_t n_rows, int64_t n_cols, int64_t *bytes) {
     QREC_REQUIRE(bytes && n_rows >= 0 && n_cols >= 0, "qrec_expo_prior_workspace_bytes: bad arguments");
-    const int64_t n_seg = std::max<int64_t>(1, (n_rows + kPriorSegment - 1) / kPriorSegment);
-    *bytes = align256(16) + align256(8 * n_seg * n_cols) + 2 * align256(8 * n_cols);
+    *bytes = layout_bytes(prior_layout, n_rows, n_cols);
     return QREC_OK;
 }
 
@@ -401,42 +408,36 @@ extern "C" int qrec_expo_prior(const double *d_X, int64_t n_rows, const double *
     QREC_REQUIRE(n_rows >= 0 && n_cols >= 0, "qrec_expo_prior: bad sizes");
     QREC_REQUIRE(d_col_indptr && d_col_indices && d_a_sum && d_ws && (d_X || n_rows == 0) && (d_F || n_cols == 0),
                  "qrec_expo_prior: null pointer");
-    int64_t need = 0;
-    qrec_expo_prior_workspace_bytes(n_rows, n_cols, &need);
-    QREC_REQUIRE(ws_bytes >= need, "qrec_expo_prior: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
+    Carver c(d_ws);
+    const PriorWs w = prior_layout(c, n_rows, n_cols);
+    QREC_REQUIRE(ws_bytes >= (int64_t)c.bytes(), "qrec_expo_prior: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)c.bytes());
     Prior pr;
     if (int e = to_prior(prior, "qrec_expo_prior", &pr)) return e;
     if (n_cols == 0) return QREC_OK;
     hipStream_t st = as_stream(stream);
-    const int n_seg = (int)std::max<int64_t>(1, (n_rows + kPriorSegment - 1) / kPriorSegment);
-    char *p = static_cast<char *>(d_ws);
-    int *status = reinterpret_cast<int *>(p); p += align256(16);
-    double *partial = reinterpret_cast<double *>(p); p += align256(8 * (int64_t)n_seg * n_cols);
-    double *a_new = reinterpret_cast<double *>(p); p += align256(8 * n_cols);
-    double *mu_new = reinterpret_cast<double *>(p);
-    expo_check_kernel<<<1, kThreads, 0, st>>>(d_col_indptr, n_cols, status);
+    expo_check_kernel<<<1, kThreads, 0, st>>>(d_col_indptr, n_cols, w.status);
     QREC_LAUNCH_CHECK();
-    const dim3 grid((unsigned)((n_cols + kThreads - 1) / kThreads), (unsigned)n_seg);
+    const dim3 grid((unsigned)((n_cols + kThreads - 1) / kThreads), (unsigned)w.n_seg);
     if (n_rows == 0) {
-        QREC_HIP_CHECK(hipMemsetAsync(partial, 0, 8 * n_cols, st));
+        QREC_HIP_CHECK(hipMemsetAsync(w.partial, 0, 8 * n_cols, st));
     } else {
         switch (ld) {
-            case 16: expo_prior_partial_kernel<1><<<grid, kThreads, 0, st>>>(d_X, n_rows, d_F, n_cols, d, pr, partial); break;
-            case 32: expo_prior_partial_kernel<2><<<grid, kThreads, 0, st>>>(d_X, n_rows, d_F, n_cols, d, pr, partial); break;
-            case 64: expo_prior_partial_kernel<4><<<grid, kThreads, 0, st>>>(d_X, n_rows, d_F, n_cols, d, pr, partial); break;
-            default: expo_prior_partial_kernel<8><<<grid, kThreads, 0, st>>>(d_X, n_rows, d_F, n_cols, d, pr, partial); break;
+            case 16: expo_prior_partial_kernel<1><<<grid, kThreads, 0, st>>>(d_X, n_rows, d_F, n_cols, d, pr, w.partial); break;
+            case 32: expo_prior_partial_kernel<2><<<grid, kThreads, 0, st>>>(d_X, n_rows, d_F, n_cols, d, pr, w.partial); break;
+            case 64: expo_prior_partial_kernel<4><<<grid, kThreads, 0, st>>>(d_X, n_rows, d_F, n_cols, d, pr, w.partial); break;
+            default: expo_prior_partial_kernel<8><<<grid, kThreads, 0, st>>>(d_X, n_rows, d_F, n_cols, d, pr, w.partial); break;
         }
         QREC_LAUNCH_CHECK();
     }
-    expo_prior_final_kernel<<<grid.x, kThreads, 0, st>>>(d_X, n_rows, d_F, n_cols, d, ld, d_col_indptr, d_col_indices, pr, partial,
-                                                         n_seg, a_new, d_mu ? mu_new : nullptr, status);
+    expo_prior_final_kernel<<<grid.x, kThreads, 0, st>>>(d_X, n_rows, d_F, n_cols, d, ld, d_col_indptr, d_col_indices, pr, w.partial,
+                                                         w.n_seg, w.a_new, d_mu ? w.mu_new : nullptr, w.status);
     QREC_LAUNCH_CHECK();
     const unsigned nb = (unsigned)std::min<int64_t>((n_cols + kThreads - 1) / kThreads, 2048);
-    expo_commit_kernel<<<nb, kThreads, 0, st>>>(d_a_sum, a_new, n_cols, status);
-    if (d_mu) expo_commit_kernel<<<nb, kThreads, 0, st>>>(d_mu, mu_new, n_cols, status);
+    expo_commit_kernel<<<nb, kThreads, 0, st>>>(d_a_sum, w.a_new, n_cols, w.status);
+    if (d_mu) expo_commit_kernel<<<nb, kThreads, 0, st>>>(d_mu, w.mu_new, n_cols, w.status);
     QREC_LAUNCH_CHECK();
     int h_status = 0;
-    QREC_HIP_CHECK(hipMemcpyAsync(&h_status, status, sizeof(int), hipMemcpyDeviceToHost, st));
+    QREC_HIP_CHECK(hipMemcpyAsync(&h_status, w.status, sizeof(int), hipMemcpyDeviceToHost, st));
     QREC_HIP_CHECK(hipStreamSynchronize(st));
     if (h_status == kOk) return QREC_OK;
     set_error(h_status == kBadIndex ? "qrec_expo_prior: a row index is outside [0, n_rows); nothing written"

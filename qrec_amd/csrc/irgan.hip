@@ -32,38 +32,11 @@ constexpr int kTile = 256;                      // items per logits workgroup
 constexpr int kItemsPerWave = 16;               // gen_item_kernel: items a wavefront walks, 64 per workgroup
 constexpr uint32_t kTagDraw = 0x69726764u;
 
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-__device__ inline float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ void philox10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0], hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 // the uniform of (seed, step, row, k) in [0, 1): 53 bits, formed as numpy's random_sample forms its doubles
 __device__ inline double draw_uniform(uint64_t seed, uint64_t step, uint32_t row, uint32_t k) {
     uint32_t c[4] = {(uint32_t)step, (uint32_t)(step >> 32), row, k};
-    philox10(c, (uint32_t)seed ^ kTagDraw, (uint32_t)(seed >> 32));
+    philox4x32_10(c, (uint32_t)seed ^ kTagDraw, (uint32_t)(seed >> 32));
     return ((double)(c[0] >> 5) * 67108864.0 + (double)(c[1] >> 6)) / 9007199254740992.0;
-}
-
-// sum of a double over the workgroup in a fixed tree; every thread must call it, every thread receives the total
-__device__ inline double block_sum_fixed(double v, double *lds) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    lds[t] = v;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (t < s) lds[t] += lds[t + s];
-        __syncthreads();
-    }
-    return lds[0];
 }
 
 // row b of the draws: the last b with ptr[b] <= s
@@ -76,14 +49,7 @@ __device__ inline int row_of(const int64_t *__restrict__ ptr, int B, int64_t s) 
     return lo;
 }
 
-__device__ inline bool in_sorted(const int32_t *__restrict__ row, int64_t len, int item) {
-    int64_t lo = 0, hi = len;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (row[mid] < item) lo = mid + 1; else hi = mid;
-    }
-    return lo < len && row[lo] == item;
-}
+__device__ inline bool in_sorted(const int32_t *__restrict__ row, int64_t len, int item) { return sorted_find(row, len, item) >= 0; }
 
 // the user's row as [P[u] | 1 | 0 ...] on the lanes of a wavefront, NK columns per lane; a user outside the table reads as zeros
 template <int NK>
@@ -295,27 +261,31 @@ int gen_sort_bytes(int64_t K, size_t *bytes) {
     const hipError_t e = rocprim::radix_sort_pairs(nullptr, tb, (const int32_t *)nullptr, (int32_t *)nullptr, rocprim::counting_iterator<int32_t>(0),
                                                    (int32_t *)nullptr, (size_t)(K > 0 ? K : 1), 0u, 32u, (hipStream_t)0);
     QREC_REQUIRE(e == hipSuccess, "irgan: rocprim::radix_sort_pairs size query failed");
-    *bytes = align256(tb ? tb : 256);
+    *bytes = align_up(tb ? tb : 256, 256);
     return QREC_OK;
 }
 inline int gen_blocks(int n_items) { return (n_items + 4 * kItemsPerWave - 1) / (4 * kItemsPerWave); }
-int gen_carve(void *ws, int n_items, int ld, int64_t K, GenWs *g, int64_t *bytes) {
+// the layout of a generator step's workspace, stated once: sized on a null base, carved on the caller's buffer
+int gen_layout(Carver &c, int n_items, int ld, int64_t K, GenWs *g) {
     size_t tb = 0;
     const int rc = gen_sort_bytes(K, &tb);
     if (rc != QREC_OK) return rc;
-    char *p = static_cast<char *>(ws);
-    const size_t kk = (size_t)(K > 0 ? K : 1);
-    g->term = reinterpret_cast<double *>(p); p += align256(kk * 8);
-    g->l2 = reinterpret_cast<double *>(p); p += align256(kk * 8);
-    g->scal = reinterpret_cast<double *>(p); p += 256;
-    g->keys = reinterpret_cast<int32_t *>(p); p += align256(kk * 4);
-    g->keys_sorted = reinterpret_cast<int32_t *>(p); p += align256(kk * 4);
-    g->slots_sorted = reinterpret_cast<int32_t *>(p); p += align256(kk * 4);
-    g->c = reinterpret_cast<float *>(p); p += (size_t)n_items * 4;
-    g->n = reinterpret_cast<int32_t *>(p); p += align256((size_t)n_items * 4);
-    g->part = reinterpret_cast<float *>(p); p += align256((size_t)gen_blocks(n_items) * ld * 4);
-    g->temp = p; g->temp_bytes = tb; p += tb;
-    *bytes = (int64_t)(p - static_cast<char *>(ws));
+    const size_t kk = (size_t)(K > 0 ? K : 1), ni = (size_t)n_items;
+    g->term = c.take<double>(kk, 256);
+    g->l2 = c.take<double>(kk, 256);
+    g->scal = c.take<double>(2, 256);
+    g->keys = c.take<int32_t>(kk, 256);
+    g->keys_sorted = c.take<int32_t>(kk, 256);
+    g->slots_sorted = c.take<int32_t>(kk, 256);
+    g->c = c.take<float>(ni, 256);
+    g->n = c.take<int32_t>(ni);                                    // right behind c: one memset clears both
+    // from here on an array is followed by the padding of its own size to 256, wherever it starts (c + n need not end on 256)
+    c.take<char>(align_up(ni * 4, 256) - ni * 4);
+    const size_t part = (size_t)gen_blocks(n_items) * ld * 4;
+    g->part = c.take<float>(part / 4);
+    c.take<char>(align_up(part, 256) - part);
+    g->temp = c.take<char>(tb);
+    g->temp_bytes = tb;
     return QREC_OK;
 }
 
@@ -519,18 +489,13 @@ int check_shape(const char *who, int n_users, int n_items, int d, int ld) {
     return QREC_OK;
 }
 
-struct RowWs { float *tile_max, *row_max; double *tile_sum, *row_sum; };
+struct RowWs { double *tile_sum, *row_sum; float *tile_max, *row_max; };      // in the order they lie
 inline int n_tiles_of(int n_items) { return (n_items + kTile - 1) / kTile; }
 inline int n_chunks_of(int n_items) { return (n_items + kChunk - 1) / kChunk; }
-RowWs row_carve(void *ws, int B, int n_items, int64_t *bytes) {
-    RowWs r;
-    const size_t nt = (size_t)n_tiles_of(n_items);
-    char *p = static_cast<char *>(ws);
-    r.tile_sum = reinterpret_cast<double *>(p); p += align256((size_t)B * nt * 8);
-    r.row_sum = reinterpret_cast<double *>(p); p += align256((size_t)B * 8);
-    r.tile_max = reinterpret_cast<float *>(p); p += align256((size_t)B * nt * 4);
-    r.row_max = reinterpret_cast<float *>(p); p += align256((size_t)B * 4);
-    *bytes = (int64_t)(p - static_cast<char *>(ws));
+RowWs row_layout(Carver &c, int B, int n_items) {
+    const size_t nt = (size_t)n_tiles_of(n_items), nb = (size_t)B;
+    const RowWs r = {c.take<double>(nb * nt, 256), c.take<double>(nb, 256), c.take<float>(nb * nt, 256), c.take<float>(nb, 256)};
+    c.pad(256);
     return r;
 }
 
@@ -547,7 +512,7 @@ extern "C" {
 
 int qrec_irgan_row_workspace_bytes(int32_t B, int32_t n_items, int64_t *bytes) {
     QREC_REQUIRE(bytes && B > 0 && n_items > 0, "qrec_irgan_row_workspace_bytes: bad argument");
-    row_carve(nullptr, B, n_items, bytes);
+    *bytes = layout_bytes(row_layout, B, n_items);
     return QREC_OK;
 }
 
@@ -562,8 +527,7 @@ int qrec_irgan_row_weights(const float *d_P, const float *d_Q, int32_t n_users, 
     QREC_REQUIRE(mode == QREC_IRGAN_NEGATIVES || (mode == QREC_IRGAN_MIXTURE && d_p), "qrec_irgan_row_weights: bad mode");
     QREC_REQUIRE(temperature > 0.0f && sample_lambda >= 0.0f && sample_lambda <= 1.0f, "qrec_irgan_row_weights: bad temperature or mixture");
     hipStream_t st = as_stream(stream);
-    int64_t nb = 0;
-    const RowWs r = row_carve(d_ws, B, n_items, &nb);
+    const RowWs r = carve(d_ws, row_layout, B, n_items);
     const int nt = n_tiles_of(n_items), nc = n_chunks_of(n_items);
     QREC_NK(ld, hipLaunchKernelGGL((logits_kernel<NK>), dim3(nt, B), dim3(256), 0, st, d_P, d_Q, n_users, n_items, d, ld, d_users, temperature,
                                    d_z, r.tile_max, r.tile_sum));
@@ -617,7 +581,10 @@ int qrec_irgan_reward(const float *d_P, const float *d_Q, int32_t n_users, int32
 int qrec_irgan_gen_workspace_bytes(int32_t n_items, int32_t ld, int64_t K, int64_t *bytes) {
     QREC_REQUIRE(bytes && n_items > 0 && ld > 0 && K >= 0 && K < ((int64_t)1 << 31), "qrec_irgan_gen_workspace_bytes: bad argument");
     GenWs g;
-    return gen_carve(nullptr, n_items, ld, K, &g, bytes);
+    Carver c(nullptr);
+    const int rc = gen_layout(c, n_items, ld, K, &g);
+    *bytes = (int64_t)c.bytes();
+    return rc;
 }
 
 int qrec_irgan_gen_step(const float *d_P, float *d_Q, float *d_mQ, float *d_vQ, int32_t n_users, int32_t n_items, int32_t d, int32_t ld,
@@ -630,9 +597,10 @@ int qrec_irgan_gen_step(const float *d_P, float *d_Q, float *d_mQ, float *d_vQ, 
                  "qrec_irgan_gen_step: bad argument");
     QREC_REQUIRE(user >= 0 && user < n_users, "qrec_irgan_gen_step: user %d outside the table", user);
     GenWs g;
-    int64_t need = 0;
-    const int rc2 = gen_carve(d_ws, n_items, ld, K, &g, &need);
+    Carver c(d_ws);
+    const int rc2 = gen_layout(c, n_items, ld, K, &g);
     if (rc2 != QREC_OK) return rc2;
+    const int64_t need = (int64_t)c.bytes();
     QREC_REQUIRE(ws_bytes >= need, "qrec_irgan_gen_step: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
     hipStream_t st = as_stream(stream);
     QREC_NK(ld, hipLaunchKernelGGL((gen_prep_kernel<NK>), dim3((unsigned)((K + 3) / 4)), dim3(256), 0, st, d_Q, n_items, ld, d_samples, d_reward, K,

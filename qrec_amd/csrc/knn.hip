@@ -394,6 +394,19 @@ __global__ __launch_bounds__(kThreads) void slopeone_predict_kernel(int64_t n_ro
     }
 }
 
+// the two workspaces; neither is stated smaller than 256 bytes
+double *topk_layout(Carver &c, int64_t n_queries, int64_t m) {       // [m][n_queries], the similarity block transposed
+    double *BT = c.take<double>((size_t)(n_queries * m));
+    c.off = std::max<size_t>(c.off, 256);
+    return BT;
+}
+struct SlopeWs { double *dev; int32_t *freq; };                      // [batch][n_items] each
+SlopeWs slope_layout(Carver &c, int64_t batch, int64_t n_items) {
+    const SlopeWs w = {c.take<double>((size_t)(batch * n_items)), c.take<int32_t>((size_t)(batch * n_items))};
+    c.off = std::max<size_t>(c.off, 256);
+    return w;
+}
+
 }  // namespace
 
 extern "C" int qrec_knn_sweep(int32_t measure, int64_t n_queries, const int64_t *d_q_indptr, const int32_t *d_q_keys,
@@ -429,7 +442,7 @@ extern "C" int qrec_knn_sweep(int32_t measure, int64_t n_queries, const int64_t 
 
 extern "C" int qrec_knn_topk_workspace_bytes(int64_t n_queries, int64_t m, int64_t *bytes) {
     QREC_REQUIRE(n_queries >= 0 && m >= 0 && bytes, "qrec_knn_topk_workspace_bytes: bad arguments");
-    *bytes = std::max<int64_t>(n_queries * m * (int64_t)sizeof(double), 256);
+    *bytes = layout_bytes(topk_layout, n_queries, m);
     return QREC_OK;
 }
 
@@ -443,13 +456,13 @@ extern "C" int qrec_knn_topk(int64_t n_queries, const double *d_S, int64_t ld_S,
     QREC_REQUIRE(k >= 1, "qrec_knn_topk: k = %d", k);
     QREC_REQUIRE(n_queries >= 0 && m >= 0 && m <= n_cands && ld_S >= n_cands, "qrec_knn_topk: bad sizes");
     QREC_REQUIRE(n_queries + n_cands < (int64_t)UINT_MAX, "qrec_knn_topk: sequence positions need 32 bits");
-    int64_t need = 0;
-    qrec_knn_topk_workspace_bytes(n_queries, m, &need);
+    Carver c(d_ws);
+    double *BT = topk_layout(c, n_queries, m);
+    const int64_t need = (int64_t)c.bytes();
     QREC_REQUIRE(ws_bytes >= need && d_ws, "qrec_knn_topk: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
     if (n_queries == 0) return QREC_OK;
     QREC_REQUIRE(n_queries <= INT_MAX, "qrec_knn_topk: too many queries");
     hipStream_t st = as_stream(stream);
-    double *BT = static_cast<double *>(d_ws);
     if (m > 0) {
         dim3 g((unsigned)((m + 31) / 32), (unsigned)((n_queries + 31) / 32));
         QREC_REQUIRE(g.y <= 65535, "qrec_knn_topk: too many queries for the transpose grid");
@@ -479,7 +492,7 @@ extern "C" int qrec_knn_predict(int32_t mode, int64_t n_rows, const int32_t *d_r
 
 extern "C" int qrec_slopeone_workspace_bytes(int64_t batch, int64_t n_items, int64_t *bytes) {
     QREC_REQUIRE(batch >= 0 && n_items >= 0 && bytes, "qrec_slopeone_workspace_bytes: bad arguments");
-    *bytes = std::max<int64_t>(batch * n_items * (int64_t)(sizeof(double) + sizeof(int32_t)), 256);
+    *bytes = layout_bytes(slope_layout, batch, n_items);
     return QREC_OK;
 }
 
@@ -490,18 +503,17 @@ extern "C" int qrec_slopeone_batch(int64_t q0, int64_t nq, const int64_t *d_q_in
                                    const int32_t *d_u_items, const double *d_u_vals, double *d_pred, int32_t *d_status, void *d_ws,
                                    int64_t ws_bytes, void *stream) {
     QREC_REQUIRE(q0 >= 0 && nq >= 0 && n_users >= 0 && n_items >= 0 && n_rows >= 0, "qrec_slopeone_batch: bad sizes");
-    int64_t need = 0;
-    qrec_slopeone_workspace_bytes(nq, n_items, &need);
+    Carver c(d_ws);
+    const SlopeWs w = slope_layout(c, nq, n_items);
+    const int64_t need = (int64_t)c.bytes();
     QREC_REQUIRE(ws_bytes >= need && d_ws, "qrec_slopeone_batch: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
     if (nq == 0) return QREC_OK;
-    double *dev = static_cast<double *>(d_ws);
-    int32_t *freq = reinterpret_cast<int32_t *>(dev + nq * n_items);
     int rc = qrec_knn_sweep(QREC_KNN_SLOPEONE, nq, d_q_indptr + q0, d_q_keys, d_q_vals, nullptr, nullptr, n_users, d_u_indptr_sorted,
-                            d_u_items_sorted, d_u_vals_sorted, nullptr, n_items, nullptr, dev, n_items, freq, n_items, stream);
+                            d_u_items_sorted, d_u_vals_sorted, nullptr, n_items, nullptr, w.dev, n_items, w.freq, n_items, stream);
     if (rc != QREC_OK) return rc;
     if (n_rows == 0) return QREC_OK;
     slopeone_predict_kernel<<<(unsigned)((n_rows + kThreads - 1) / kThreads), kThreads, 0, as_stream(stream)>>>(
-        n_rows, d_row_query, d_row_user, d_row_base, q0, nq, dev, freq, n_items, n_users, d_u_indptr, d_u_items, d_u_vals, d_pred,
+        n_rows, d_row_query, d_row_user, d_row_base, q0, nq, w.dev, w.freq, n_items, n_users, d_u_indptr, d_u_items, d_u_vals, d_pred,
         d_status);
     QREC_LAUNCH_CHECK();
     return QREC_OK;

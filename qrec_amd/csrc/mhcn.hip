@@ -23,20 +23,6 @@ using namespace qrec;
 
 namespace {
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ void philox10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-        const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-        const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
 template <int LPR>
 __device__ __forceinline__ float group_bcast(const f32x4 &v, int j, int lane) {
     // column j of the row held by this lane's group: lane (j >> 2) of the group, component j & 3
@@ -78,7 +64,7 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const float *__restrict__
         const int64_t off = (live ? row : n - 1) * LD + 4 * r;
         const f32x4 x = *reinterpret_cast<const f32x4 *>(X + off);
         const f32x4 z = row_times_matrix<LPR>(x, s_w, b4, lane, r);
-        const f32x4 s = {sigmoidf_(z.x), sigmoidf_(z.y), sigmoidf_(z.z), sigmoidf_(z.w)};
+        const f32x4 s = {sigmoidf(z.x), sigmoidf(z.y), sigmoidf(z.z), sigmoidf(z.w)};
         if (live) {
             *reinterpret_cast<f32x4 *>(S + off) = s;
             *reinterpret_cast<f32x4 *>(Y + off) = x * s;
@@ -271,7 +257,7 @@ __global__ __launch_bounds__(256) void hss_coef_kernel(const float *__restrict__
         float pos = dot(m, e), neg1 = dot(m1, e), neg2 = dot(e2, m), pg = dot(e, gr), ng = dot(e3, gr);
         pos = row_allreduce_sum<LPR>(pos); neg1 = row_allreduce_sum<LPR>(neg1); neg2 = row_allreduce_sum<LPR>(neg2);
         pg = row_allreduce_sum<LPR>(pg); ng = row_allreduce_sum<LPR>(ng);
-        const float s1 = sigmoidf_(pos - neg1), s2 = sigmoidf_(neg1 - neg2), s3 = sigmoidf_(pg - ng);
+        const float s1 = sigmoidf(pos - neg1), s2 = sigmoidf(neg1 - neg2), s3 = sigmoidf(pg - ng);
         const float c1 = -(1.f - s1), c2 = -(1.f - s2), c3 = -(1.f - s3);
         if (r == 0) {
             const f32x4 cf = {c1, c2 - c1, -c2, c3};
@@ -343,7 +329,7 @@ __global__ void perm_keys_kernel(int64_t n, int64_t total, uint64_t seed, uint64
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     uint32_t c[4] = {(uint32_t)i, (uint32_t)(i >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32)};
-    philox10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     const uint64_t seg = (uint64_t)(i / n);
     keys[i] = (seg << 40) | ((((uint64_t)c[0] << 32) | c[1]) >> 24);
     idx[i] = (int32_t)(i % n);
@@ -361,11 +347,29 @@ __global__ void small_perm_kernel(int32_t n, int32_t count, uint64_t seed, uint6
     for (int i = 0; i < n; i++) p[i] = i;
     for (int i = n - 1; i >= 1; i--) {
         uint32_t c[4] = {(uint32_t)i, (uint32_t)t, (uint32_t)stream_id, (uint32_t)(stream_id >> 32)};
-        philox10(c, (uint32_t)seed, (uint32_t)(seed >> 32) ^ 0x5bd1e995u);
+        philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32) ^ 0x5bd1e995u);
         const int j = (int)(((uint64_t)c[0] * (uint64_t)(i + 1)) >> 32);
         const int32_t tmp = p[i]; p[i] = p[j]; p[j] = tmp;
     }
     for (int i = 0; i < n; i++) q[p[i]] = i;
+}
+
+// ---- the three scratch layouts, packed floats (column sums are [kColBlocks][256] whatever the row stride) ----------------
+struct AttWs { float *dv, *part; };                  // [256] the summed dv, [kColBlocks][256] the blocks' partial column sums
+AttWs att_layout(Carver &c) { return {c.take<float>(256), c.take<float>((size_t)kColBlocks * 256)}; }
+struct HssWs { float *graph, *dgraph, *part, *coef; };      // [256] [256] (one memset clears both) [kColBlocks][256] [n_rows][4]
+HssWs hss_layout(Carver &c, int64_t n_rows) {
+    return {c.take<float>(256), c.take<float>(256), c.take<float>((size_t)kColBlocks * 256), c.take<float>(4 * (size_t)n_rows)};
+}
+struct PermWs { void *temp; size_t temp_bytes; uint64_t *keys_in, *keys_out; int32_t *idx; };   // the sort's temp, then [total] each
+int perm_layout(Carver &c, size_t total, PermWs *w) {
+    w->temp_bytes = 0;
+    QREC_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, w->temp_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, total));
+    w->temp = c.take<char>(w->temp_bytes);
+    w->keys_in = c.take<uint64_t>(total, 256);
+    w->keys_out = c.take<uint64_t>(total);
+    w->idx = c.take<int32_t>(total);
+    return QREC_OK;
 }
 
 template <int LPR>
@@ -441,18 +445,19 @@ int qrec_channel_attention_bwd(const float *d_dOut, const float *d_e1, const flo
                  d_g_att && d_g_att_mat && n_rows >= 0, "qrec_channel_attention_bwd: bad argument");
     hipStream_t st = as_stream(stream);
     QREC_REQUIRE(ld == 32 || ld == 64 || ld == 128 || ld == 256, "qrec_channel_attention_bwd: row stride must be 32, 64, 128 or 256 floats (got %d)", ld);
+    const AttWs w = carve(d_dv_scratch, att_layout);
     int blocks = 0;
     if (n_rows > 0) {
         QREC_MHCN_LD_SWITCH("qrec_channel_attention_bwd", {
             blocks = launch_rows<LPR>(n_rows); if (blocks > kColBlocks) blocks = kColBlocks;
             hipLaunchKernelGGL((att_bwd_kernel<LPR>), dim3((unsigned)blocks), dim3(256), 0, st, d_dOut, d_e1, d_e2, d_e3, d_score, d_v, n_rows,
-                               d_de1, d_de2, d_de3, accumulate, d_dhalf, half_accumulate, d_dv_scratch + 256);
+                               d_de1, d_de2, d_de3, accumulate, d_dhalf, half_accumulate, w.part);
         })
         QREC_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3(1), dim3(256), 0, st, d_dv_scratch + 256, blocks, ld, 1.0f, 0, d_dv_scratch);
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3(1), dim3(256), 0, st, w.part, blocks, ld, 1.0f, 0, w.dv);
     QREC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(att_param_kernel, dim3(1), dim3(256), 0, st, d_dv_scratch, d_att_mat, d_att, ld, d_g_att_mat, d_g_att);
+    hipLaunchKernelGGL(att_param_kernel, dim3(1), dim3(256), 0, st, w.dv, d_att_mat, d_att, ld, d_g_att_mat, d_g_att);
     QREC_LAUNCH_CHECK();
     return QREC_OK;
 }
@@ -466,17 +471,17 @@ int qrec_hss_loss_grad(const float *d_em, const float *d_edge, int64_t n_rows, i
                  d_scratch && d_dem && d_dedge && d_loss && n_rows >= 0 && d >= 1 && d <= ld, "qrec_hss_loss_grad: bad argument");
     if (n_rows == 0) return QREC_OK;
     hipStream_t st = as_stream(stream);
-    float *graph = d_scratch, *dgraph = d_scratch + 256, *part = d_scratch + 512, *coef = part + kColBlocks * 256;   // [256] [256] [512][256] [n][4]
-    QREC_HIP_CHECK(hipMemsetAsync(d_scratch, 0, sizeof(float) * 512, st));       // the pad columns of graph / dgraph stay zero
+    const HssWs w = carve(d_scratch, hss_layout, n_rows);
+    QREC_HIP_CHECK(hipMemsetAsync(w.graph, 0, sizeof(float) * 512, st));           // graph and dgraph: their pad columns stay zero
     QREC_MHCN_LD_SWITCH("qrec_hss_loss_grad", {
         int blocks = launch_rows<LPR>(n_rows); if (blocks > kColBlocks) blocks = kColBlocks;
-        hipLaunchKernelGGL((col_sum_kernel<LPR>), dim3((unsigned)blocks), dim3(256), 0, st, d_edge, n_rows, part);
-        hipLaunchKernelGGL(colsum_finish_kernel, dim3(1), dim3(256), 0, st, part, blocks, ld, 1.0f / (float)n_rows, 0, graph);
-        hipLaunchKernelGGL((hss_coef_kernel<LPR>), dim3((unsigned)blocks), dim3(256), 0, st, d_em, d_edge, d_p1, d_p2, d_k2, d_p3, d_k3, graph, d,
-                           n_rows, coef, part, d_loss);
-        hipLaunchKernelGGL(colsum_finish_kernel, dim3(1), dim3(256), 0, st, part, blocks, ld, 1.0f, 0, dgraph);
-        hipLaunchKernelGGL((hss_grad_kernel<LPR>), dim3((unsigned)launch_rows<LPR>(n_rows)), dim3(256), 0, st, d_em, d_edge, coef, d_p1, d_p1inv,
-                           d_p2, d_p2inv, d_k2, d_k2inv, d_p3inv, d_k3inv, graph, dgraph, d, n_rows, scale, d_dem, d_dedge);
+        hipLaunchKernelGGL((col_sum_kernel<LPR>), dim3((unsigned)blocks), dim3(256), 0, st, d_edge, n_rows, w.part);
+        hipLaunchKernelGGL(colsum_finish_kernel, dim3(1), dim3(256), 0, st, w.part, blocks, ld, 1.0f / (float)n_rows, 0, w.graph);
+        hipLaunchKernelGGL((hss_coef_kernel<LPR>), dim3((unsigned)blocks), dim3(256), 0, st, d_em, d_edge, d_p1, d_p2, d_k2, d_p3, d_k3, w.graph, d,
+                           n_rows, w.coef, w.part, d_loss);
+        hipLaunchKernelGGL(colsum_finish_kernel, dim3(1), dim3(256), 0, st, w.part, blocks, ld, 1.0f, 0, w.dgraph);
+        hipLaunchKernelGGL((hss_grad_kernel<LPR>), dim3((unsigned)launch_rows<LPR>(n_rows)), dim3(256), 0, st, d_em, d_edge, w.coef, d_p1, d_p1inv,
+                           d_p2, d_p2inv, d_k2, d_k2inv, d_p3inv, d_k3inv, w.graph, w.dgraph, d, n_rows, scale, d_dem, d_dedge);
     })
     QREC_LAUNCH_CHECK();
     return QREC_OK;
@@ -484,23 +489,23 @@ int qrec_hss_loss_grad(const float *d_em, const float *d_edge, int64_t n_rows, i
 
 int qrec_hss_scratch_bytes(int64_t n_rows, int64_t *bytes) {
     QREC_REQUIRE(bytes && n_rows >= 0, "qrec_hss_scratch_bytes: bad argument");
-    *bytes = (int64_t)sizeof(float) * (512 + kColBlocks * 256 + 4 * n_rows);
+    *bytes = layout_bytes(hss_layout, n_rows);
     return QREC_OK;
 }
 
 int qrec_channel_attention_scratch_bytes(int64_t *bytes) {
     QREC_REQUIRE(bytes, "qrec_channel_attention_scratch_bytes: bad argument");
-    *bytes = (int64_t)sizeof(float) * (256 + kColBlocks * 256);       // dv, then the blocks' partial column sums
+    *bytes = layout_bytes(att_layout);
     return QREC_OK;
 }
 
 int qrec_random_permutations_scratch_bytes(int64_t n, int32_t count, int64_t *bytes) {
     QREC_REQUIRE(bytes && n >= 0 && count >= 0 && count < (1 << 20) && n * count < ((int64_t)1 << 31), "qrec_random_permutations_scratch_bytes: bad argument");
-    const size_t total = (size_t)n * (size_t)count;
-    size_t tmp = 0;
-    QREC_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp, (uint64_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, total));
-    *bytes = (int64_t)(((tmp + 255) / 256) * 256 + total * (8 + 8 + 4));
-    return QREC_OK;
+    PermWs w;
+    Carver c(nullptr);
+    const int rc = perm_layout(c, (size_t)n * (size_t)count, &w);
+    *bytes = (int64_t)c.bytes();
+    return rc;
 }
 
 int qrec_random_permutations(int64_t n, int32_t count, uint64_t seed, uint64_t stream_id, void *d_scratch, int32_t *d_perms,
@@ -509,15 +514,13 @@ int qrec_random_permutations(int64_t n, int32_t count, uint64_t seed, uint64_t s
     const int64_t total = n * count;
     if (total == 0) return QREC_OK;
     hipStream_t st = as_stream(stream);
-    size_t tmp = 0;
-    QREC_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp, (uint64_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)total));
-    char *base = static_cast<char *>(d_scratch);
-    const size_t tmp_pad = ((tmp + 255) / 256) * 256;
-    uint64_t *keys_in = reinterpret_cast<uint64_t *>(base + tmp_pad), *keys_out = keys_in + total;
-    int32_t *idx = reinterpret_cast<int32_t *>(keys_out + total);
-    hipLaunchKernelGGL(perm_keys_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n, total, seed, stream_id, keys_in, idx);
+    PermWs w;
+    Carver c(d_scratch);
+    const int rc = perm_layout(c, (size_t)total, &w);
+    if (rc != QREC_OK) return rc;
+    hipLaunchKernelGGL(perm_keys_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n, total, seed, stream_id, w.keys_in, w.idx);
     QREC_LAUNCH_CHECK();
-    QREC_HIP_CHECK(rocprim::radix_sort_pairs(base, tmp, keys_in, keys_out, idx, d_perms, (size_t)total, 0, 64, st));
+    QREC_HIP_CHECK(rocprim::radix_sort_pairs(w.temp, w.temp_bytes, w.keys_in, w.keys_out, w.idx, d_perms, (size_t)total, 0, 64, st));
     if (d_invs) {
         hipLaunchKernelGGL(invert_perm_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_perms, n, total, d_invs);
         QREC_LAUNCH_CHECK();

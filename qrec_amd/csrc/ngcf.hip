@@ -20,18 +20,6 @@ using namespace qrec;
 
 namespace {
 
-__device__ __forceinline__ void philox10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-        const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-        const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
 // pre[32 rows][ld] = (side + E) W1 + (E*side) W2      NT = ld/32 output column tiles
 // Persistent blocks: the two weight matrices are staged in LDS once per block (2 x LD*LD floats) and every
 // wavefront walks 32-row tiles.  A operand: the lane's own row, 8 float4 loads per table and 64-column chunk;
@@ -126,12 +114,12 @@ __global__ __launch_bounds__(256) void activate_rows_kernel(float *__restrict__ 
             } else {
                 const int64_t grow = row + philox_row0;      // the table row this block row stands for (row-partitioned tables)
                 uint32_t c[4] = {(uint32_t)grow, (uint32_t)(grow >> 32) ^ ((uint32_t)r << 8), (uint32_t)stream_id, (uint32_t)(stream_id >> 32)};
-                philox10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+                philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
                 // tf.nn.dropout: keep iff uniform >= 1 - keep_prob
-                fac.x = ((float)(c[0] >> 8) * 0x1p-24f >= 1.f - keep) ? 1.f / keep : 0.f;
-                fac.y = ((float)(c[1] >> 8) * 0x1p-24f >= 1.f - keep) ? 1.f / keep : 0.f;
-                fac.z = ((float)(c[2] >> 8) * 0x1p-24f >= 1.f - keep) ? 1.f / keep : 0.f;
-                fac.w = ((float)(c[3] >> 8) * 0x1p-24f >= 1.f - keep) ? 1.f / keep : 0.f;
+                fac.x = (uniform24(c[0]) >= 1.f - keep) ? 1.f / keep : 0.f;
+                fac.y = (uniform24(c[1]) >= 1.f - keep) ? 1.f / keep : 0.f;
+                fac.z = (uniform24(c[2]) >= 1.f - keep) ? 1.f / keep : 0.f;
+                fac.w = (uniform24(c[3]) >= 1.f - keep) ? 1.f / keep : 0.f;
             }
         }
         auto lrelu = [](float x) { return fmaxf(0.2f * x, x); };

@@ -22,8 +22,6 @@ using namespace qrec;
 
 namespace {
 
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int sort_temp_bytes(int64_t n, size_t *bytes) {
     static thread_local int64_t last_n = -1;
     static thread_local size_t last_bytes = 0;
@@ -35,7 +33,7 @@ int sort_temp_bytes(int64_t n, size_t *bytes) {
     const hipError_t e = rocprim::radix_sort_pairs(nullptr, tb, (const int32_t *)nullptr, (int32_t *)nullptr,
                                                    rocprim::counting_iterator<int32_t>(0), (int32_t *)nullptr, (size_t)n, 0u, 32u, (hipStream_t)0);
     QREC_REQUIRE(e == hipSuccess, "ordered scatter: rocprim::radix_sort_pairs size query failed");
-    *bytes = align256(tb ? tb : 256);
+    *bytes = align_up(tb ? tb : 256, 256);
     last_n = n; last_bytes = *bytes; last_dev = dev;
     return QREC_OK;
 }
@@ -65,32 +63,37 @@ __global__ __launch_bounds__(256) void ordered_scatter_kernel(const int32_t *__r
     }
 }
 
+int ordered_layout(Carver &c, int64_t n_slots, int ld, OrderedScatterWs *w) {
+    const int rc = sort_temp_bytes(n_slots > 0 ? n_slots : 1, &w->temp_bytes);
+    if (rc != QREC_OK) return rc;
+    w->contrib = c.take<float>((size_t)n_slots * ld, 256);
+    w->keys = c.take<int32_t>((size_t)n_slots, 256);
+    w->keys_sorted = c.take<int32_t>((size_t)n_slots, 256);
+    w->slots_sorted = c.take<int32_t>((size_t)n_slots, 256);
+    w->temp = c.take<char>(w->temp_bytes, 256);
+    return QREC_OK;
+}
+
 }  // namespace
 
 namespace qrec {
 
 int ordered_ws_bytes(int64_t n_slots, int ld, int64_t *bytes) {
-    size_t tb = 0;
-    const int rc = sort_temp_bytes(n_slots > 0 ? n_slots : 1, &tb);
-    if (rc != QREC_OK) return rc;
-    *bytes = (int64_t)(align256((size_t)n_slots * ld * 4) + 3 * align256((size_t)n_slots * 4) + tb);
-    return QREC_OK;
+    OrderedScatterWs w;
+    Carver c(nullptr);
+    const int rc = ordered_layout(c, n_slots, ld, &w);
+    *bytes = (int64_t)c.bytes();
+    return rc;
 }
 
 int ordered_ws_carve(void *ws, int64_t ws_bytes, int64_t n_slots, int ld, OrderedScatterWs *w) {
-    int64_t need = 0;
-    const int rc = ordered_ws_bytes(n_slots, ld, &need);
+    Carver c(ws);
+    const int rc = ordered_layout(c, n_slots, ld, w);
     if (rc != QREC_OK) return rc;
-    QREC_REQUIRE(ws && ws_bytes >= need, "ordered scatter: workspace of %lld bytes, %lld needed (qrec_ordered_scatter_workspace_bytes)",
-                 (long long)ws_bytes, (long long)need);
+    QREC_REQUIRE(ws && ws_bytes >= (int64_t)c.bytes(), "ordered scatter: workspace of %lld bytes, %lld needed (qrec_ordered_scatter_workspace_bytes)",
+                 (long long)ws_bytes, (long long)c.bytes());
     QREC_REQUIRE(n_slots < ((int64_t)1 << 31), "ordered scatter: at most 2^31 - 1 slots");
-    char *p = static_cast<char *>(ws);
-    w->contrib = reinterpret_cast<float *>(p); p += align256((size_t)n_slots * ld * 4);
-    w->keys = reinterpret_cast<int32_t *>(p); p += align256((size_t)n_slots * 4);
-    w->keys_sorted = reinterpret_cast<int32_t *>(p); p += align256((size_t)n_slots * 4);
-    w->slots_sorted = reinterpret_cast<int32_t *>(p); p += align256((size_t)n_slots * 4);
-    w->temp = p;
-    return sort_temp_bytes(n_slots > 0 ? n_slots : 1, &w->temp_bytes);
+    return QREC_OK;
 }
 
 int ordered_scatter_run(const OrderedScatterWs &w, int64_t n_slots, int ld, int64_t class_size, float *out, hipStream_t st) {

@@ -1093,3 +1093,14 @@ def test_oracle_on_row_disjoint_chunks_does_not_depend_on_the_chunk_order(block,
     assert np.array_equal(Pa, Pb) and np.array_equal(Qa, Qb)
     assert abs(la - lb) <= 1e-12 * abs(la)
     assert np.array_equal(Pa[-3:], P0[-3:]) and np.array_equal(Qa[-3:], Q0[-3:]) and not np.array_equal(Pa[:-3], P0[:-3])
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    """tests/golden/workspace_bytes.json: what every workspace-size entry point that answers without a device returned before each
+    layout was stated once (csrc/common.h, Carver).  The sizes are ABI -- a caller may have sized its buffer with an older build --
+    so they hold exactly, at shapes on both sides of every padding and segment boundary (tests/workspace_cases.py)."""
+    from workspace_cases import CPU_CASES, stated_bytes
+    recorded = json.load(open(os.path.join(GOLDEN, "workspace_bytes.json")))["cpu"]
+    assert [(fn, args) for fn, args, _ in recorded] == [(fn, args) for fn, args in CPU_CASES]
+    got = [[fn, args, stated_bytes(capi, fn, args)] for fn, args in CPU_CASES]
+    assert got == recorded, [(g, r[2]) for g, r in zip(got, recorded) if g != r][:10]
