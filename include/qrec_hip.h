@@ -1097,6 +1097,55 @@ int qrec_irgan_assemble_rows(const int32_t *d_users, int32_t n_users, int32_t B,
                              const int64_t *d_draw_ptr, const int32_t *d_samples, const int64_t *d_row_ptr, int64_t n_rows, int32_t *d_out_u,
                              int32_t *d_out_i, float *d_out_label, void *stream);
 
+/* ---- CFGAN: model/ranking/CFGAN.py (csrc/cfgan.hip) -------------------------------------------------------------------------
+ * Generator r^ = sigmoid(C G_W1 + G_b1) with G_W1 [n_items][ld] (ld a multiple of 32, >= n_items, padding columns zero and kept
+ * zero) and G_b1 [ld]; discriminator D(x) = sigmoid(x . D_W1 + D_b1) over x = [r^ * mask | C] (fake) and [C | C] (real), its
+ * 2 n_items + 1 values in ONE array d_thetaD (D_W1 flat, then D_b1).  The batch is in CDAE's list format with everything kept:
+ * "in" = the rated entries of the batch rows (C[n,i] = in_val), "live" = the mask positions, and the per-slot array in the place
+ * of lv_label is a FLAG: 1 where the position is in N_zr as well.  n_in / n_live are the entry counts (list pointers are clamped
+ * to them, ids outside a table are skipped, never dereferenced).  fp32, fp64 loss sums, no float atomics: every sum has one order
+ * (list order inside a batch row, ascending batch row inside an item) and two launches give the same bits.
+ * n_items > QREC_CFGAN_MAX_ITEMS returns QREC_ERR_UNSUPPORTED (three n_items^2 fp32 tables must fit the device).
+ *
+ * qrec_cfgan_forward: at the live slots z = sum_i C[n,i] W[i][j] + b[j] (ascending i), r^ = sigmoid(z); per batch row the two
+ *   logits, a_r = -(1/B) D_r (1 - D_r) / (D_r + 1e-4), a_f = (1/B) D_f (1 - D_f) / (1 - D_f + 1e-4) (1 - sigmoid(x) evaluated as
+ *   sigmoid(-x)), delta = (-a_f D_W1[j] + alpha flag r^) r^ (1 - r^) per slot, and
+ *     d_losses[0] = D_loss = -mean(log(D_r + 1e-4) + log(1 - D_f + 1e-4)),
+ *     d_losses[1] = G_loss = mean log(1 - D_f + 1e-4) + alpha / 2 sum over flagged slots of r^2      -- all left in the workspace.
+ * qrec_cfgan_dis_step (after forward on the same lists): the gradient of D_loss over the item-major views, real and fake pass
+ *   summed apart and then added, and TF's Adam (alpha from the host) on the 2 n_items + 1 values in the same launch;
+ *   d_grad_out (may be null) [2 n_items + 1] receives the gradient.
+ * qrec_cfgan_gen_sweep (after forward): ONE pass over W, m, v -- each read once and written once in 16-byte accesses.  Per tile
+ *   (row i, QREC_CFGAN_CHUNK columns) the gradient gW[i][j] = sum_n C[n,i] delta[n,j] is staged in LDS from the batch rows that
+ *   rated i (ascending batch row) and Adam is applied; rows no batch user rated take the Adam update all the same (momentum).
+ *   The bias is one more row, gb[j] = sum_n delta[n,j].  d_gradW_out [n_items][ld] / d_gradb_out [ld] (may be null) receive
+ *   the gradient.
+ * qrec_cfgan_read_slots: copies of r^, delta [n_live] and a_r, a_f [B] out of the workspace (each may be null).
+ * Workspace: qrec_cfgan_workspace_bytes(B, n_live), shared by the calls of a step. */
+#define QREC_CFGAN_CHUNK 1024
+#define QREC_CFGAN_MAX_ITEMS 131072
+int qrec_cfgan_workspace_bytes(int32_t B, int64_t n_live, int64_t *bytes);
+int qrec_cfgan_forward(const float *d_W, const float *d_b, const float *d_thetaD, int32_t n_items, int32_t ld, int32_t B, int64_t n_in,
+                       int64_t n_live, const int32_t *d_in_ptr, const int32_t *d_in_item, const float *d_in_val, const int32_t *d_lv_ptr,
+                       const int32_t *d_lv_item, const int32_t *d_lv_flag, float alpha, void *d_ws, double *d_losses, void *stream);
+int qrec_cfgan_dis_step(float *d_thetaD, float *d_mD, float *d_vD, int32_t n_items, int32_t B, int64_t n_in, int64_t n_live,
+                        const int32_t *d_in_cptr, const int32_t *d_in_crow, const float *d_in_cval, const int32_t *d_lv_cptr,
+                        const int32_t *d_lv_crow, const int32_t *d_lv_cslot, void *d_ws, float adam_alpha, float beta1, float beta2, float eps,
+                        float *d_grad_out, void *stream);
+int qrec_cfgan_gen_sweep(float *d_W, float *d_mW, float *d_vW, float *d_b, float *d_mb, float *d_vb, int32_t n_items, int32_t ld, int32_t B,
+                         int64_t n_in, int64_t n_live, const int32_t *d_in_cptr, const int32_t *d_in_crow, const float *d_in_cval,
+                         const int32_t *d_lv_ptr, const int32_t *d_lv_item, const int32_t *d_lv_cptr, const int32_t *d_lv_cslot, void *d_ws,
+                         float adam_alpha, float beta1, float beta2, float eps, float *d_gradW_out, float *d_gradb_out, void *stream);
+int qrec_cfgan_read_slots(const void *d_ws, int32_t B, int64_t n_live, float *d_rhat, float *d_delta, float *d_a_r, float *d_a_f, void *stream);
+/* qrec_score_topk's BLOCK route for CFGAN's evaluation (CFGAN.py:129-134): the score block is FILLED from the rated CSR with
+ * values (d_rated_indptr int64 [n_users + 1], rows ascending), S[item][b] = sum over the rated i of user b, ascending i, of
+ * C[u,i] d_W[i][item] -- no users x items input is formed -- then sigmoid(S + d_item_bias[item]), rated items to 0, top-N. */
+int qrec_score_topk_sparse_row_sigmoid_bias_scratch_bytes(int32_t n_items, int32_t n_batch_users, int64_t *bytes);
+int qrec_score_topk_sparse_row_sigmoid_bias(const float *d_W, const float *d_item_bias, int32_t ld, int32_t n_items,
+                                            const int32_t *d_user_ids, int32_t n_batch_users, const int64_t *d_rated_indptr,
+                                            const int32_t *d_rated_items, const float *d_rated_vals, int32_t N, void *d_scratch,
+                                            int32_t *d_ids_out, float *d_scores_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

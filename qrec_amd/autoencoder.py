@@ -300,3 +300,160 @@ class CdaeTrainer:
         capi.cdae_encode(self.W_enc, self.b_enc, self.V, self.ni, self.nu, self.nh, self.ld, d(users, np.int32), users.size, d(ptr, np.int32),
                          d(items[order], np.int32), d(vals[order], np.float32), out, stream)
         return out
+
+
+# ---- CFGAN (model/ranking/CFGAN.py; csrc/cfgan.hip) ---------------------------------------------------------------------------------
+def cfgan_lists(users, n_items: int, pos_rows, pos_items, pos_vals, mask_rows, mask_items, zr_rows, zr_items) -> BatchLists:
+    """CFGAN's batch in CDAE's list form with everything kept: ``pos_*`` the rated entries of every batch row (the "in" lists, C[n,i]),
+    ``mask_*`` the sampled negatives of ``mask`` (with the rated items they make the "live" lists), ``zr_*`` the sampled negatives of
+    ``N_zr``.  ``lv_label`` of the result is the per-live-slot FLAG of N_zr and mask: the zero-reconstruction term lives only where
+    the two independent draws coincide (CFGAN.py:107)."""
+    L = lists_from_entries(users, n_items, pos_rows, pos_items, pos_vals, mask_rows, mask_items, lambda r, i: np.ones(len(r), bool))
+    zr = np.unique(np.asarray(zr_rows, np.int64) * n_items + np.asarray(zr_items, np.int64))
+    lv_row = np.repeat(np.arange(L.B, dtype=np.int64), np.diff(L.lv_ptr))
+    L.lv_label = np.ascontiguousarray(np.isin(lv_row * n_items + L.lv_item, zr), np.int32)
+    return L
+
+
+def cfgan_lists_from_dense(users, C, mask, N_zr) -> BatchLists:
+    """the reference's three dense feeds of one epoch (CFGAN.py:123) in list form"""
+    C = np.asarray(C); mask = np.asarray(mask) != 0
+    if (~mask & (C != 0)).any():
+        raise ValueError("cfgan_lists_from_dense: the mask must hold every rated item")
+    pr, pi = np.nonzero(C)
+    mr, mi = np.nonzero(mask & (C == 0))
+    zr, zi = np.nonzero(np.asarray(N_zr) != 0)
+    return cfgan_lists(users, C.shape[1], pr, pi, C[pr, pi], mr, mi, zr, zi)
+
+
+class CfganTrainer:
+    """CFGAN.py:46-127 on the device.  Variables as the reference shapes them: G_W1 [n_items, n_items], G_b1 [n_items], D_W1
+    [2 n_items, 1], D_b1 [1]; on the device G_W1 has row stride ld (n_items rounded up to 32, padding zero) and the discriminator's
+    2 n_items + 1 values lie in one array.  One epoch is a discriminator step and three generator steps on one batch, each with the
+    forward pass at the current variables; the two Adam optimizers keep separate beta powers.  The generator's step is one sweep over
+    G_W1 and its two Adam slots (qrec_cfgan_gen_sweep): no [n_items, n_items] gradient exists unless ``keep_gradients`` asks for it.
+    No kernel here uses a float atomic: ``ordered_reductions`` has nothing to switch."""
+
+    def __init__(self, G_W1, G_b1, D_W1, D_b1, lr: float, alpha: float = 0.01, keep_gradients: bool = False):
+        G_W1 = np.asarray(G_W1, np.float32)
+        self.ni = ni = G_W1.shape[0]
+        D_W1 = np.asarray(D_W1, np.float32).reshape(-1); D_b1 = np.asarray(D_b1, np.float32).reshape(-1)
+        if G_W1.shape != (ni, ni) or np.shape(G_b1) != (ni,) or D_W1.size != 2 * ni or D_b1.size != 1:
+            raise ValueError("CfganTrainer: G_W1 [n_items, n_items], G_b1 [n_items], D_W1 [2 n_items, 1], D_b1 [1]")
+        if ni > capi.CFGAN_MAX_ITEMS:
+            raise ValueError(f"CFGAN on the device supports up to {capi.CFGAN_MAX_ITEMS} items")
+        self.ld = ld = -(-ni // 32) * 32
+        self.n_d = -(-(2 * ni + 1) // 4) * 4
+        self.lr, self.alpha = float(lr), float(alpha)
+        W = np.zeros((ni, ld), np.float32); W[:, :ni] = G_W1
+        b = np.zeros(ld, np.float32); b[:ni] = G_b1
+        tD = np.zeros(self.n_d, np.float32); tD[:2 * ni] = D_W1; tD[2 * ni] = D_b1[0]
+        self.W, self.b, self.thetaD = DeviceBuffer.from_numpy(W), DeviceBuffer.from_numpy(b), DeviceBuffer.from_numpy(tD)
+        z = lambda a: DeviceBuffer.zeros(a.shape, np.float32)
+        self.mW, self.vW, self.mb, self.vb, self.mD, self.vD = z(W), z(W), z(b), z(b), z(tD), z(tD)
+        self.gW, self.gb, self.gD = (z(W), z(b), z(tD)) if keep_gradients else (None, None, None)
+        f = np.float32
+        self._b1, self._b2, self._eps = f(0.9), f(0.999), f(1e-8)
+        self._pow = {"D": [self._b1, self._b2], "G": [self._b1, self._b2]}          # beta powers, advanced after each step of that optimizer
+        self.losses = DeviceBuffer.zeros(8, np.float64)     # (D_loss, G_loss) of the forward pass of the D step and of the three G steps
+        self._loss_at = [DeviceSlice(self.losses, 2 * k, (2,)) for k in range(4)]
+        self._g_steps = 0
+        self._B = self._slots = 0
+        self._stage = None
+        self.ws = None
+
+    to_device = CdaeTrainer.to_device
+
+    def _reserve(self, B: int, n_live: int):
+        if B > self._B or n_live > self._slots:
+            self._B, self._slots = max(B, self._B), max(max(n_live, 1) * 5 // 4 + 64, self._slots)
+            self.ws = DeviceBuffer(capi.cfgan_workspace_bytes(self._B, self._slots), np.uint8)
+
+    def _adam_alpha(self, which: str) -> float:
+        f = np.float32
+        b1p, b2p = self._pow[which]
+        alpha = float(f(f(self.lr) * np.sqrt(f(1) - b2p, dtype=f) / (f(1) - b1p)))
+        self._pow[which] = [f(b1p * self._b1), f(b2p * self._b2)]
+        return alpha
+
+    def _prepare(self, lists: BatchLists, stream) -> BatchLists:
+        if lists.n_items != self.ni:
+            raise ValueError("CfganTrainer: the lists are over another item count")
+        if lists.B < 1:
+            raise ValueError("CfganTrainer: an empty batch")
+        self._reserve(lists.B, lists.n_live)
+        return self.to_device(lists, stream)
+
+    def forward(self, lists: BatchLists, stream=None, slot: int = 0) -> BatchLists:
+        """r_hat and delta at the live slots, the row quantities and both losses at the current variables (no update)"""
+        L = self._prepare(lists, stream)
+        capi.cfgan_forward(self.W, self.b, self.thetaD, self.ni, self.ld, L, self.alpha, self.ws, self._loss_at[slot], stream)
+        return L
+
+    def dis_step_async(self, lists: BatchLists, stream=None) -> BatchLists:
+        L = self.forward(lists, stream, 0)
+        capi.cfgan_dis_step(self.thetaD, self.mD, self.vD, self.ni, L, self.ws, self._adam_alpha("D"), float(self._b1), float(self._b2),
+                            float(self._eps), self.gD, stream)
+        self._g_steps = 0
+        return L
+
+    def gen_step_async(self, lists: BatchLists, stream=None) -> BatchLists:
+        L = self.forward(lists, stream, 1 + self._g_steps % 3)
+        capi.cfgan_gen_sweep(self.W, self.mW, self.vW, self.b, self.mb, self.vb, self.ni, self.ld, L, self.ws, self._adam_alpha("G"),
+                             float(self._b1), float(self._b2), float(self._eps), self.gW, self.gb, stream)
+        self._g_steps += 1
+        return L
+
+    def train_epoch_async(self, lists: BatchLists, stream=None):
+        """CFGAN.py:120-125: D, G, G, G on one batch (uploaded once)"""
+        L = self.dis_step_async(lists, stream)
+        for _ in range(3):
+            self.gen_step_async(L, stream)
+
+    def d_loss(self, stream=None) -> float:
+        """D_loss of the epoch's discriminator step, at the variables the step started from (what the reference prints)"""
+        return float(self.losses.numpy(stream)[0])
+
+    def g_losses(self, stream=None) -> np.ndarray:
+        """G_loss of the generator steps since the last discriminator step (three after an epoch)"""
+        return self.losses.numpy(stream)[3:3 + 2 * min(self._g_steps, 3):2].copy()
+
+    def g_loss(self, stream=None) -> float:
+        """G_loss of the last generator step (what the reference prints)"""
+        return float(self.g_losses(stream)[-1])
+
+    def slots(self, L: BatchLists) -> dict:
+        """r_hat, delta per live slot and a_r, a_f per batch row of the last forward pass"""
+        n, B = L.n_live, L.B
+        out = dict(r=DeviceBuffer.zeros(max(n, 1), np.float32), delta=DeviceBuffer.zeros(max(n, 1), np.float32),
+                   a_r=DeviceBuffer.zeros(B, np.float32), a_f=DeviceBuffer.zeros(B, np.float32))
+        capi.cfgan_read_slots(self.ws, B, n, out["r"], out["delta"], out["a_r"], out["a_f"])
+        return {k: v.numpy()[:n if k in ("r", "delta") else B] for k, v in out.items()}
+
+    # ---- read-back ----------------------------------------------------------------------------------------------------------
+    def parameters(self) -> dict:
+        """the four variables in the reference's shapes"""
+        ni = self.ni
+        tD = self.thetaD.numpy()
+        return dict(G_W1=self.W.numpy()[:, :ni].copy(), G_b1=self.b.numpy()[:ni].copy(), D_W1=tD[:2 * ni].reshape(2 * ni, 1).copy(),
+                    D_b1=tD[2 * ni:2 * ni + 1].copy())
+
+    def raw_gradients(self, which: str) -> dict:
+        """``"D"``: the gradients the last discriminator step applied; ``"G"``: those of the last generator step"""
+        if self.gW is None:
+            raise RuntimeError("CfganTrainer: built without keep_gradients")
+        ni = self.ni
+        if which == "D":
+            g = self.gD.numpy()
+            return dict(D_W1=g[:2 * ni].reshape(2 * ni, 1).copy(), D_b1=g[2 * ni:2 * ni + 1].copy())
+        if which == "G":
+            return dict(G_W1=self.gW.numpy()[:, :ni].copy(), G_b1=self.gb.numpy()[:ni].copy())
+        raise ValueError("raw_gradients: 'D' or 'G'")
+
+    def padding_is_zero(self) -> bool:
+        ni = self.ni
+        tabs = [a.numpy()[:, ni:] for a in (self.W, self.mW, self.vW)] + [a.numpy()[ni:] for a in (self.b, self.mb, self.vb)]
+        tabs += [a.numpy()[2 * ni + 1:] for a in (self.thetaD, self.mD, self.vD)]
+        if self.gW is not None:
+            tabs += [self.gW.numpy()[:, ni:], self.gb.numpy()[ni:]]
+        return not any(x.any() for x in tabs)

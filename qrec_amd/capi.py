@@ -203,6 +203,14 @@ _SIGNATURES = {
                             _vp, _vp, _vp, _i64, _vp],
     "qrec_irgan_dis_slots": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "qrec_irgan_assemble_rows": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "qrec_cfgan_workspace_bytes": [_i32, _i64, _vp],
+    "qrec_cfgan_forward": [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp],
+    "qrec_cfgan_dis_step": [_vp, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp],
+    "qrec_cfgan_gen_sweep": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32,
+                             _f32, _f32, _vp, _vp, _vp],
+    "qrec_cfgan_read_slots": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp],
+    "qrec_score_topk_sparse_row_sigmoid_bias_scratch_bytes": [_i32, _i32, _vp],
+    "qrec_score_topk_sparse_row_sigmoid_bias": [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"qrec_last_error": C.c_char_p, "qrec_ratings_rows": C.c_int64, "qrec_ratings_count": C.c_int32,
              "qrec_ratings_names_bytes": C.c_int64, "qrec_ratings_free": None}
@@ -1621,3 +1629,54 @@ def irgan_assemble_rows(d_users, n_users: int, B: int, d_pos_indptr, d_pos_items
                         d_out_i, d_out_label, stream=None):
     _check(load().qrec_irgan_assemble_rows(_dp(d_users), n_users, B, _dp(d_pos_indptr), _dp(d_pos_items), _dp(d_draw_ptr), _dp(d_samples),
                                            _dp(d_row_ptr), n_rows, _dp(d_out_u), _dp(d_out_i), _dp(d_out_label), _sh(stream)))
+
+
+# ---- CFGAN (csrc/cfgan.hip; the contract is in include/qrec_hip.h) ---------------------------------------------------------------
+CFGAN_CHUNK = 1024
+CFGAN_MAX_ITEMS = 131072
+
+
+def cfgan_workspace_bytes(B: int, n_live: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_cfgan_workspace_bytes(B, n_live, C.byref(out)))
+    return out.value
+
+
+def cfgan_forward(d_W, d_b, d_thetaD, n_items: int, ld: int, L, alpha: float, d_ws, d_losses, stream=None):
+    """``L``: a BatchLists on the device whose ``lv_label`` carries the N_zr flag"""
+    _check(load().qrec_cfgan_forward(_dp(d_W), _dp(d_b), _dp(d_thetaD), n_items, ld, L.B, L.n_in, L.n_live, _dp(L.in_ptr), _dp(L.in_item),
+                                     _dp(L.in_val), _dp(L.lv_ptr), _dp(L.lv_item), _dp(L.lv_label), alpha, _dp(d_ws), _dp(d_losses),
+                                     _sh(stream)))
+
+
+def cfgan_dis_step(d_thetaD, d_mD, d_vD, n_items: int, L, d_ws, adam_alpha: float, beta1: float, beta2: float, eps: float, d_grad_out=None,
+                   stream=None):
+    _check(load().qrec_cfgan_dis_step(_dp(d_thetaD), _dp(d_mD), _dp(d_vD), n_items, L.B, L.n_in, L.n_live, _dp(L.in_cptr), _dp(L.in_crow),
+                                      _dp(L.in_cval), _dp(L.lv_cptr), _dp(L.lv_crow), _dp(L.lv_cslot), _dp(d_ws), adam_alpha, beta1, beta2, eps,
+                                      _dp(d_grad_out), _sh(stream)))
+
+
+def cfgan_gen_sweep(d_W, d_mW, d_vW, d_b, d_mb, d_vb, n_items: int, ld: int, L, d_ws, adam_alpha: float, beta1: float, beta2: float,
+                    eps: float, d_gradW_out=None, d_gradb_out=None, stream=None):
+    _check(load().qrec_cfgan_gen_sweep(_dp(d_W), _dp(d_mW), _dp(d_vW), _dp(d_b), _dp(d_mb), _dp(d_vb), n_items, ld, L.B, L.n_in, L.n_live,
+                                       _dp(L.in_cptr), _dp(L.in_crow), _dp(L.in_cval), _dp(L.lv_ptr), _dp(L.lv_item), _dp(L.lv_cptr),
+                                       _dp(L.lv_cslot), _dp(d_ws), adam_alpha, beta1, beta2, eps, _dp(d_gradW_out), _dp(d_gradb_out),
+                                       _sh(stream)))
+
+
+def cfgan_read_slots(d_ws, B: int, n_live: int, d_rhat=None, d_delta=None, d_a_r=None, d_a_f=None, stream=None):
+    _check(load().qrec_cfgan_read_slots(_dp(d_ws), B, n_live, _dp(d_rhat), _dp(d_delta), _dp(d_a_r), _dp(d_a_f), _sh(stream)))
+
+
+def score_topk_sparse_row_sigmoid_bias_scratch_bytes(n_items: int, n_batch_users: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_score_topk_sparse_row_sigmoid_bias_scratch_bytes(n_items, n_batch_users, C.byref(out)))
+    return out.value
+
+
+def score_topk_sparse_row_sigmoid_bias(d_W, d_item_bias, ld: int, n_items: int, d_user_ids, n_batch_users: int, d_rated_indptr,
+                                       d_rated_items, d_rated_vals, N: int, d_scratch, d_ids_out, d_scores_out, stream=None):
+    """the block route with the score block filled from the rated CSR with values, then sigmoid(S + bias[item]) (fp32)"""
+    _check(load().qrec_score_topk_sparse_row_sigmoid_bias(_dp(d_W), _dp(d_item_bias), ld, n_items, _dp(d_user_ids), n_batch_users,
+                                                          _dp(d_rated_indptr), _dp(d_rated_items), _dp(d_rated_vals), N, _dp(d_scratch),
+                                                          _dp(d_ids_out), _dp(d_scores_out), _sh(stream)))

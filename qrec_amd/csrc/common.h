@@ -74,6 +74,11 @@ int ordered_scatter_run(const OrderedScatterWs &w, int64_t n_slots, int ld, int6
 // qrec_score_topk_sigmoid_bias runs between scoring and masking)
 int score_block_sigmoid_bias(float *S_T, const float *bias, int n_items, int b_pad, hipStream_t st);
 
+// S[item][b] = sum over the rated items i of user_ids[b], in CSR order, of vals * W[i][item]: the fill pass of
+// qrec_score_topk_sparse_row_sigmoid_bias (cfgan.hip), in the place of the MFMA scoring of the block route
+struct SparseRows { const float *W; int ld; const int64_t *indptr; const int32_t *items; const float *vals; };
+int score_block_sparse_rows(float *S_T, const SparseRows &r, int n_items, const int32_t *user_ids, int n_b, int b_pad, hipStream_t st);
+
 // ---- buffer resources: the only way to get 16-byte loads/stores with an explicit cache
 // policy (sc1 = bypass the non-coherent per-XCD caches) and compiler-tracked waitcnts.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

@@ -1413,7 +1413,8 @@ __global__ void scatter_rows_kernel(const int32_t *__restrict__ flagged_list, in
 template <typename T>
 int run_score_topk(const void *U, const void *V, int d, int ld, int n_items, const int32_t *user_ids,
                    int n_b, const int64_t *rated_indptr, const int32_t *rated_items, int K, void *scratch,
-                   int32_t *ids_out, void *scores_out, hipStream_t st, const float *item_bias = nullptr) {
+                   int32_t *ids_out, void *scores_out, hipStream_t st, const float *item_bias = nullptr,
+                   const qrec::SparseRows *sparse = nullptr) {
     constexpr int TILE = sizeof(T) == 4 ? 32 : 16;         // items per MFMA tile
     constexpr int UTILE = sizeof(T) == 4 ? 64 : 16;        // users per wavefront (fp32: two 32-user tiles)
     const int b_pad = (n_b + 63) / 64 * 64;
@@ -1426,7 +1427,12 @@ int run_score_topk(const void *U, const void *V, int d, int ld, int n_items, con
     const int waves_per_utile = (n_item_tiles + per_wave - 1) / per_wave;
     const dim3 grid((unsigned)n_utiles, (unsigned)((waves_per_utile + 3) / 4));
     T *S_T = static_cast<T *>(scratch);
-    if constexpr (sizeof(T) == 4)
+    if (sparse) {              // qrec_score_topk_sparse_row_sigmoid_bias: the block comes from the rated CSR, not from U V^T
+        if constexpr (sizeof(T) == 4) {
+            const int rc = qrec::score_block_sparse_rows(S_T, *sparse, n_items, user_ids, n_b, b_pad, st);
+            if (rc != QREC_OK) return rc;
+        }
+    } else if constexpr (sizeof(T) == 4)
         hipLaunchKernelGGL(score_kernel_f32, grid, dim3(256), 0, st, (const float *)U, (const float *)V, ld,
                            n_items, user_ids, n_b, b_pad, per_wave, S_T, 1, (int64_t)64, (int64_t)1);
     else
@@ -1948,6 +1954,31 @@ int qrec_score_topk_sigmoid_bias(const float *d_U, const float *d_V, const float
     if (n_batch_users == 0) return QREC_OK;
     return run_score_topk<float>(d_U, d_V, d, ld, n_items, d_user_ids, n_batch_users, d_rated_indptr, d_rated_items, K, d_scratch,
                                  d_ids_out, d_scores_out, as_stream(stream), d_item_bias);
+}
+
+int qrec_score_topk_sparse_row_sigmoid_bias_scratch_bytes(int32_t n_items, int32_t n_batch_users, int64_t *bytes) {
+    QREC_REQUIRE(bytes && n_items >= 0 && n_batch_users >= 0, "qrec_score_topk_sparse_row_sigmoid_bias_scratch_bytes: bad arguments");
+    *bytes = (int64_t)block_path_bytes(4, n_items, n_batch_users);
+    return QREC_OK;
+}
+
+int qrec_score_topk_sparse_row_sigmoid_bias(const float *d_W, const float *d_item_bias, int32_t ld, int32_t n_items,
+                                            const int32_t *d_user_ids, int32_t n_batch_users, const int64_t *d_rated_indptr,
+                                            const int32_t *d_rated_items, const float *d_rated_vals, int32_t K, void *d_scratch,
+                                            int32_t *d_ids_out, float *d_scores_out, void *stream) {
+    QREC_REQUIRE(d_W && d_item_bias && d_user_ids && d_rated_indptr && d_rated_items && d_rated_vals && d_scratch && d_ids_out && d_scores_out,
+                 "qrec_score_topk_sparse_row_sigmoid_bias: null argument");
+    QREC_REQUIRE(n_items >= 1 && ld >= n_items && n_batch_users >= 0, "qrec_score_topk_sparse_row_sigmoid_bias: bad sizes");
+    QREC_REQUIRE(ld % 32 == 0, "qrec_score_topk_sparse_row_sigmoid_bias: the row stride must be a multiple of 32 floats (got ld=%d)", ld);
+    QREC_REQUIRE(K >= 1 && K <= 100, "qrec_score_topk_sparse_row_sigmoid_bias: N must be in 1..100 (base/recommender.py:132-134)");
+    if (n_items > QREC_CFGAN_MAX_ITEMS) {
+        ::qrec::set_error("qrec_score_topk_sparse_row_sigmoid_bias: %d items above the supported %d", n_items, QREC_CFGAN_MAX_ITEMS);
+        return QREC_ERR_UNSUPPORTED;
+    }
+    if (n_batch_users == 0) return QREC_OK;
+    const qrec::SparseRows rows{d_W, ld, d_rated_indptr, d_rated_items, d_rated_vals};
+    return run_score_topk<float>(nullptr, nullptr, 1, 32, n_items, d_user_ids, n_batch_users, d_rated_indptr, d_rated_items, K, d_scratch,
+                                 d_ids_out, d_scores_out, as_stream(stream), d_item_bias, &rows);
 }
 
 int qrec_rank_hits(const int32_t *d_ids, int32_t n_batch_users, int32_t row_stride, int32_t n_cut,

@@ -147,6 +147,33 @@ class SigmoidBiasRanker(DeviceRanker):
                                      self.rated[0] if self.rated else None, self.rated[1] if self.rated else None, N, scratch, d_ids, d_sc)
 
 
+class SparseRowSigmoidRanker(DeviceRanker):
+    """scores = sigmoid(sum_i C[u,i] W[i] + bias) over the user's whole rating row, rated train items then set to 0 (CFGAN.py:129-134
+    + base/recommender.py:147-149): the block route with its score block FILLED from the rated CSR with values
+    (qrec_score_topk_sparse_row_sigmoid_bias) -- an SpMM against the trainer's own [n_items][ld] table; no users x items input is
+    formed and nothing but the CSR is uploaded.  ``topk`` slices the users to the scratch budget as the base class does."""
+
+    def __init__(self, d_W, d_bias, n_users: int, n_items: int, ld: int, rated: CSR):
+        if rated is None or rated.values is None:
+            raise ValueError("SparseRowSigmoidRanker: the rated CSR must carry the ratings")
+        if rated.indptr.size != n_users + 1:
+            raise ValueError("SparseRowSigmoidRanker: the CSR must have one row per user")
+        self._init_state(np.float32, n_items, ld, n_users, n_items, rated)
+        srt = rated.sorted_rows()
+        self.d_vals = DeviceBuffer.from_numpy(srt.values.astype(np.float32) if srt.values.size else np.zeros(1, np.float32))
+        self.dW, self.d_bias = d_W, d_bias
+
+    def update_tables(self, d_W, d_bias):
+        self.dW, self.d_bias = d_W, d_bias
+
+    def _scratch_bytes(self, n_batch_users: int, N: int) -> int:
+        return capi.score_topk_sparse_row_sigmoid_bias_scratch_bytes(self.n_items, n_batch_users)
+
+    def _score_topk(self, d_users, n: int, N: int, scratch, d_ids, d_sc):
+        capi.score_topk_sparse_row_sigmoid_bias(self.dW, self.d_bias, self.ld, self.n_items, d_users, n, self.rated[0], self.rated[1],
+                                                self.d_vals, N, scratch, d_ids, d_sc)
+
+
 def ranking_measure_strings(test_lens, per_n: dict, Ns) -> list:
     """The strings of Measure.rankingMeasure (util/measure.py:24-49) from per-user hit counts and DCG sums:
     ``per_n[n] = (hits, dcg)`` sequences in testSet_u order, ``test_lens[k] = len(testSet_u[user_k])``.  Same
