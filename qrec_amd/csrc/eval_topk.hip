@@ -336,10 +336,6 @@ __global__ __launch_bounds__(kHeapThreads) void heap_topk_kernel(const T *__rest
 // sequential emulation: few of them -> one wavefront each (exact_wave_kernel: 64 items per step, ballot for the
 // first item above the heap root, lane 0 runs heapq's sift), many -> the lane-per-user kernel above.
 constexpr int kSlices = 16;
-__host__ inline size_t score_block_bytes(size_t elem, int n_items, int n_b) {
-    const size_t b_pad = ((size_t)n_b + 63) / 64 * 64, rows = ((size_t)n_items + 31) / 32 * 32;
-    return rows * b_pad * elem;
-}
 
 // (a1) per-user maxima over kGroups disjoint item ranges (pure streaming, kGroups lanes per user), then tau[b] = the
 //      M-th largest of them: M DIFFERENT items reach tau, so the user's M best scores all do -- a valid threshold, and a
@@ -1246,12 +1242,7 @@ __global__ __launch_bounds__(64 * kSelectWaves) void select_topk_kernel(
     // share of the pool (a few elements each)
     for (int e = lane; e < total; e += 64) {
         const int32_t item = 0x7fffffff - (int32_t)(unsigned)(pool[e] & 0xffffffffu);
-        int64_t lo = rbeg, hi = rend;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (rated_sorted[mid] < item) lo = mid + 1; else hi = mid;
-        }
-        const bool rated = lo < rend && rated_sorted[lo] == item;
+        const bool rated = sorted_find(rated_sorted + rbeg, rend - rbeg, item) >= 0;
         if (rated) pool[e] = 0ull;
         kept += rated ? 0 : 1;
     }
@@ -1410,6 +1401,31 @@ __global__ void scatter_rows_kernel(const int32_t *__restrict__ flagged_list, in
     sc_out[dst] = sc_in[t];
 }
 
+// The block route's scratch: the transposed score block (items padded to the 32-item tile, users to 64), then what the sliced
+// top-N keeps behind it.  Below 8,192 items only the block is touched; the size is the same either way.
+template <typename T>
+struct BlockWs {
+    T *S_T, *gmax, *tau, *cand_s;
+    int32_t *cand_i, *cand_n, *flags, *flagged_list, *n_flagged;
+};
+template <typename T>
+BlockWs<T> block_layout(Carver &c, int n_items, int n_b) {
+    const size_t b_pad = ((size_t)n_b + 63) / 64 * 64, rows = ((size_t)n_items + 31) / 32 * 32, cand_rows = (size_t)kSlices * kSliceCap;
+    BlockWs<T> w;
+    w.S_T = c.take<T>(rows * b_pad);                       // [rows][b_pad]
+    w.gmax = c.take<T>(kGroups * b_pad);                   // group maxima [kGroups][b_pad]
+    w.tau = c.take<T>(b_pad);
+    w.cand_s = c.take<T>(cand_rows * b_pad);               // candidate rows [kSlices * kSliceCap][b_pad]: scores, ids
+    w.cand_i = c.take<int32_t>(cand_rows * b_pad);
+    w.cand_n = c.take<int32_t>(kSlices * b_pad);           // per-slice counts [kSlices][b_pad]
+    w.flags = c.take<int32_t>(b_pad);
+    w.flagged_list = c.take<int32_t>(b_pad);
+    w.n_flagged = c.take<int32_t>(16);                     // one counter: 4 of these 64 bytes are used, the rest stays because the size is ABI
+    return w;
+}
+template <typename T>
+int64_t block_path_bytes(int n_items, int n_b) { return layout_bytes(block_layout<T>, n_items, n_b); }
+
 template <typename T>
 int run_score_topk(const void *U, const void *V, int d, int ld, int n_items, const int32_t *user_ids,
                    int n_b, const int64_t *rated_indptr, const int32_t *rated_items, int K, void *scratch,
@@ -1426,7 +1442,8 @@ int run_score_topk(const void *U, const void *V, int d, int ld, int n_items, con
     if (per_wave < 8) per_wave = n_item_tiles < 8 ? n_item_tiles : 8;
     const int waves_per_utile = (n_item_tiles + per_wave - 1) / per_wave;
     const dim3 grid((unsigned)n_utiles, (unsigned)((waves_per_utile + 3) / 4));
-    T *S_T = static_cast<T *>(scratch);
+    const BlockWs<T> w = carve(scratch, block_layout<T>, n_items, n_b);
+    T *S_T = w.S_T;
     if (sparse) {              // qrec_score_topk_sparse_row_sigmoid_bias: the block comes from the rated CSR, not from U V^T
         if constexpr (sizeof(T) == 4) {
             const int rc = qrec::score_block_sparse_rows(S_T, *sparse, n_items, user_ids, n_b, b_pad, st);
@@ -1464,54 +1481,41 @@ int run_score_topk(const void *U, const void *V, int d, int ld, int n_items, con
     }
     const int per_group = (n_items + kGroups - 1) / kGroups, n_groups_used = (n_items + per_group - 1) / per_group;
     const int per_slice = (n_items + kSlices - 1) / kSlices;
-    // scratch behind the score block: group maxima [kGroups][b_pad], tau, candidate rows [kSlices*kSliceCap][b_pad] (scores,
-    // ids), per-slice counts, flags, flagged list, counter
-    unsigned char *extra = static_cast<unsigned char *>(scratch) + score_block_bytes(sizeof(T), n_items, n_b);
-    const size_t cand_rows = (size_t)kSlices * kSliceCap;
-    T *gmax = reinterpret_cast<T *>(extra);
-    T *tau = gmax + (size_t)kGroups * b_pad;
-    T *cand_s = tau + b_pad;
-    int32_t *cand_i = reinterpret_cast<int32_t *>(cand_s + cand_rows * b_pad);
-    int32_t *cand_n = cand_i + cand_rows * b_pad;
-    int32_t *flags = cand_n + (size_t)kSlices * b_pad;
-    int32_t *flagged_list = flags + b_pad;
-    int32_t *n_flagged = flagged_list + b_pad;
-    QREC_HIP_CHECK(hipMemsetAsync(n_flagged, 0, sizeof(int32_t), st));
+    QREC_HIP_CHECK(hipMemsetAsync(w.n_flagged, 0, sizeof(int32_t), st));
     const size_t lds_m = (size_t)M * kHeapThreads * (sizeof(T) + sizeof(int32_t));
     QREC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&merge_topk_kernel<T>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
     const unsigned lane_blocks = (unsigned)((n_b + 255) / 256);
     if (n_groups_used < kGroups)      // ranges past the end (n_items not a multiple): -inf maxima
         hipLaunchKernelGGL(fill_neg_inf_kernel<T>, dim3(lane_blocks, kGroups - n_groups_used), dim3(256), 0, st,
-                           gmax + (size_t)n_groups_used * b_pad, b_pad, n_b);
+                           w.gmax + (size_t)n_groups_used * b_pad, b_pad, n_b);
     hipLaunchKernelGGL(group_max_kernel<T>, dim3(lane_blocks, (unsigned)n_groups_used), dim3(256), 0, st, S_T, n_items, b_pad, n_b,
-                       per_group, gmax);
+                       per_group, w.gmax);
     QREC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(threshold_kernel<T>, dim3(lane_blocks), dim3(256), 0, st, gmax, b_pad, n_b, M, tau);
+    hipLaunchKernelGGL(threshold_kernel<T>, dim3(lane_blocks), dim3(256), 0, st, w.gmax, b_pad, n_b, M, w.tau);
     QREC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(filter_kernel<T>, dim3(lane_blocks, kSlices), dim3(256), 0, st, S_T, n_items, b_pad, n_b, per_slice, tau,
-                       cand_s, cand_i, cand_n);
+    hipLaunchKernelGGL(filter_kernel<T>, dim3(lane_blocks, kSlices), dim3(256), 0, st, S_T, n_items, b_pad, n_b, per_slice, w.tau,
+                       w.cand_s, w.cand_i, w.cand_n);
     QREC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(merge_topk_kernel<T>, dim3(user_blocks), dim3(kHeapThreads), lds_m, st, cand_s, cand_i, cand_n, b_pad, n_b, K,
-                       ids_out, (T *)scores_out, flags, n_flagged, flagged_list);
+    hipLaunchKernelGGL(merge_topk_kernel<T>, dim3(user_blocks), dim3(kHeapThreads), lds_m, st, w.cand_s, w.cand_i, w.cand_n, b_pad, n_b, K,
+                       ids_out, (T *)scores_out, w.flags, w.n_flagged, w.flagged_list);
     QREC_LAUNCH_CHECK();
     // users whose N+1 best scores are not pairwise distinct: exact emulation (device-side choice of the regime)
     const int many = n_b / 16 > 256 ? n_b / 16 : 256;
     const int wave_blocks = n_b < many ? n_b : many;
     if (K <= 64)
         hipLaunchKernelGGL((exact_wave_kernel<T, true>), dim3((unsigned)wave_blocks), dim3(64), 0, st, S_T,
-                           n_items, b_pad, K, n_flagged, flagged_list, many, ids_out, (T *)scores_out, (int64_t)64, (int64_t)1);
+                           n_items, b_pad, K, w.n_flagged, w.flagged_list, many, ids_out, (T *)scores_out, (int64_t)64, (int64_t)1);
     else
         hipLaunchKernelGGL((exact_wave_kernel<T, false>), dim3((unsigned)wave_blocks), dim3(64), (size_t)K * (sizeof(T) + sizeof(int32_t)), st, S_T,
-                           n_items, b_pad, K, n_flagged, flagged_list, many, ids_out, (T *)scores_out, (int64_t)64, (int64_t)1);
+                           n_items, b_pad, K, w.n_flagged, w.flagged_list, many, ids_out, (T *)scores_out, (int64_t)64, (int64_t)1);
     QREC_LAUNCH_CHECK();
     hipLaunchKernelGGL(heap_topk_kernel<T>, dim3(user_blocks), dim3(kHeapThreads), lds, st, S_T, n_items, b_pad, n_b, K, ids_out,
-                       (T *)scores_out, flags, n_flagged, many);
+                       (T *)scores_out, w.flags, w.n_flagged, many);
     QREC_LAUNCH_CHECK();
     return QREC_OK;
 }
 
-// geometry shared by the scratch-size query and the launch
 // ---- (A) of the fused evaluation: the threshold without a sampled score block --------------------------------------------
 // sample_max_kernel_f32: the scoring loop over every kSampleStride-th item tile, but nothing is stored: per GROUP of
 // `tiles_per_group` consecutive sampled tiles every user keeps the largest (unmasked) score and its item.
@@ -1636,12 +1640,7 @@ __global__ __launch_bounds__(256) void threshold_var_kernel(const float *__restr
         if (!(best > -__builtin_huge_valf())) break;
         if (rated_indptr) {
             const int item = garg[(int64_t)arg * b_pad + b];
-            int64_t lo = rbeg, hi = rend;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (rated_sorted[mid] < item) lo = mid + 1; else hi = mid;
-            }
-            if (lo < rend && rated_sorted[lo] == item) continue;   // the group's best is a rated item: the group is out
+            if (sorted_find(rated_sorted + rbeg, rend - rbeg, item) >= 0) continue;   // the group's best is a rated item: the group is out
         }
         th = best;
         found++;
@@ -1652,16 +1651,10 @@ __global__ __launch_bounds__(256) void threshold_var_kernel(const float *__restr
 struct FusedGeom {
     int b_pad, n_utiles, n_item_tiles, grid_x, grid_y, n_lists, list_cap, nu, n_s_tiles, n_s, fb_users;
     bool use_bf16;
-    size_t off_ub, off_vb, off_un, off_vmax, off_taul, off_gmax, off_garg, off_tau, off_cs, off_ci, off_cn, off_flags, off_list, off_nf, off_fbu, off_fbi, off_fbs, off_fb, total;
 };
 __host__ inline bool fused_ok(int dtype, int ld, int n_items, int K) {
     // one predicate for the scratch-size query and the launch (QREC_EVAL_BLOCK_PATH forces the block route in both)
     return dtype == QREC_F32 && ld <= 128 && K + 1 <= kGroups && n_items >= 64 * kSampleStride * 32 && !getenv("QREC_EVAL_BLOCK_PATH");
-}
-__host__ inline size_t block_path_bytes(size_t elem, int n_items, int n_b) {
-    const size_t b_pad = ((size_t)n_b + 63) / 64 * 64;
-    return score_block_bytes(elem, n_items, n_b) + (size_t)(kGroups + 1) * b_pad * elem + (size_t)kSlices * kSliceCap * b_pad * (elem + 4) +
-           (size_t)(kSlices + 2) * b_pad * 4 + 64;
 }
 __host__ inline FusedGeom fused_geometry(int n_items, int n_b, int ld) {
     FusedGeom g;
@@ -1688,58 +1681,75 @@ __host__ inline FusedGeom fused_geometry(int n_items, int n_b, int ld) {
     g.fb_users = (n_b / 16 > 256 ? n_b / 16 : 256);
     if (g.fb_users > n_b) g.fb_users = n_b;
     g.fb_users = (g.fb_users + 63) / 64 * 64;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    size_t o = 0;
-    g.off_ub = o; o += up((size_t)g.b_pad * ld * 2);                          // bf16 copies of the batch's user rows and of the items
-    g.off_vb = o; o += up((size_t)g.n_item_tiles * 32 * ld * 2);
-    g.off_un = o; o += up((size_t)g.b_pad * 4);
-    g.off_vmax = o; o += 256;
-    g.off_taul = o; o += up((size_t)g.b_pad * 4);
-    g.off_gmax = o; o += up((size_t)kMaxGroups * g.b_pad * 4);
-    g.off_garg = o; o += up((size_t)kMaxGroups * g.b_pad * 4);
-    g.off_tau = o; o += up((size_t)g.b_pad * 4);
-    g.off_cs = o; o += up((size_t)g.b_pad * g.n_lists * g.list_cap * 4);
-    g.off_ci = o; o += up((size_t)g.b_pad * g.n_lists * g.list_cap * 4);
-    g.off_cn = o; o += up((size_t)g.b_pad * g.n_lists * 4);
-    g.off_flags = o; o += up((size_t)g.b_pad * 4);
-    g.off_list = o; o += up((size_t)g.b_pad * 4);
-    g.off_nf = o; o += 256;
-    g.off_fbu = o; o += up((size_t)g.fb_users * 4);
-    g.off_fbi = o; o += up((size_t)g.fb_users * 100 * 4);
-    g.off_fbs = o; o += up((size_t)g.fb_users * 100 * 4);
-    g.off_fb = o; o += up(block_path_bytes(4, n_items, g.fb_users));
-    g.total = o;
     return g;
+}
+
+// The fused route's scratch.  Every array starts on a 256-byte boundary and so does the end; v_max and n_flagged are one element each.
+struct FusedWs {
+    __bf16 *Ub, *Vb;
+    float *u_norm, *v_max, *tau_low, *gmax;
+    int32_t *garg;
+    float *tau, *cand_s;
+    int32_t *cand_i, *cand_n, *flags, *flagged_list, *n_flagged, *fb_users, *fb_ids;
+    float *fb_sc, *fb_block;
+};
+FusedWs fused_layout(Carver &c, const FusedGeom &g, int n_items, int ld) {
+    const size_t b_pad = g.b_pad, cands = b_pad * g.n_lists * g.list_cap;
+    FusedWs w;
+    w.Ub = c.take<__bf16>(b_pad * ld, 256);                                   // bf16 copies of the batch's user rows and of the items
+    w.Vb = c.take<__bf16>((size_t)g.n_item_tiles * 32 * ld, 256);
+    w.u_norm = c.take<float>(b_pad, 256);
+    w.v_max = c.take<float>(1, 256);
+    w.tau_low = c.take<float>(b_pad, 256);
+    w.gmax = c.take<float>(kMaxGroups * b_pad, 256);
+    w.garg = c.take<int32_t>(kMaxGroups * b_pad, 256);
+    w.tau = c.take<float>(b_pad, 256);
+    w.cand_s = c.take<float>(cands, 256);
+    w.cand_i = c.take<int32_t>(cands, 256);
+    w.cand_n = c.take<int32_t>(b_pad * g.n_lists, 256);
+    w.flags = c.take<int32_t>(b_pad, 256);
+    w.flagged_list = c.take<int32_t>(b_pad, 256);
+    w.n_flagged = c.take<int32_t>(1, 256);
+    w.fb_users = c.take<int32_t>(g.fb_users, 256);                            // stage (D), fb_users flagged users at a time: their ids, lists
+    w.fb_ids = c.take<int32_t>((size_t)g.fb_users * 100, 256);
+    w.fb_sc = c.take<float>((size_t)g.fb_users * 100, 256);
+    // ... and their scores, in a region the size of the block layout at fb_users (the size is ABI).  Stage (D) keeps user-major
+    // [user][item] rows there: they fill exactly the layout's first array, the score block, and nothing behind it is used.
+    w.fb_block = c.take<float>(block_path_bytes<float>(n_items, g.fb_users) / sizeof(float), 256);
+    c.pad(256);
+    return w;
+}
+
+// ld -> the template arguments of the fused route's kernels, stated once.  fp32 scoring and the selection: NC column chunks of 64.
+// bf16 kernels: NM MFMA steps of 16 columns and NU user tiles per wavefront (FusedGeom::nu: 4, or 2 at ld = 128 and under QREC_EVAL_NU=2).
+template <int V> using int_c = std::integral_constant<int, V>;
+template <typename F> void with_nc(int ld, F f) { if (ld <= 64) f(int_c<1>{}); else f(int_c<2>{}); }
+template <typename F> void with_nm_nu(int ld, int nu, F f) {
+    if (ld == 32) f(int_c<2>{}, int_c<4>{});
+    else if (ld == 64) { if (nu == 2) f(int_c<4>{}, int_c<2>{}); else f(int_c<4>{}, int_c<4>{}); }
+    else f(int_c<8>{}, int_c<2>{});
 }
 
 int run_fused_topk_f32(const float *U, const float *V, int d, int ld, int n_items, const int32_t *user_ids, int n_b,
                        const int64_t *rated_indptr, const int32_t *rated_sorted, int K, void *scratch, int32_t *ids_out,
                        float *scores_out, hipStream_t st) {
     const FusedGeom g = fused_geometry(n_items, n_b, ld);
-    unsigned char *base = static_cast<unsigned char *>(scratch);
-    float *gmax = reinterpret_cast<float *>(base + g.off_gmax), *tau = reinterpret_cast<float *>(base + g.off_tau);
-    float *cand_s = reinterpret_cast<float *>(base + g.off_cs);
-    int32_t *cand_i = reinterpret_cast<int32_t *>(base + g.off_ci), *cand_n = reinterpret_cast<int32_t *>(base + g.off_cn);
-    int32_t *flags = reinterpret_cast<int32_t *>(base + g.off_flags), *flagged_list = reinterpret_cast<int32_t *>(base + g.off_list);
-    int32_t *n_flagged = reinterpret_cast<int32_t *>(base + g.off_nf);
+    const FusedWs w = carve(scratch, fused_layout, g, n_items, ld);
     const int M = K + 1;
     const int bf16_stride_env = getenv("QREC_EVAL_BF16_STRIDE") ? atoi(getenv("QREC_EVAL_BF16_STRIDE")) : 1;
     const bool use_bf16 = g.use_bf16;
     const int bf16_stride = bf16_stride_env < 1 ? 1 : (bf16_stride_env > kSampleStride ? kSampleStride : bf16_stride_env);
-    __bf16 *Ub = reinterpret_cast<__bf16 *>(base + g.off_ub), *Vb = reinterpret_cast<__bf16 *>(base + g.off_vb);
-    float *u_norm = reinterpret_cast<float *>(base + g.off_un), *v_max = reinterpret_cast<float *>(base + g.off_vmax);
-    float *tau_low = reinterpret_cast<float *>(base + g.off_taul);
     if (use_bf16) {
         // bf16 copies of the batch's user rows (gathered) and of the items, with |u_b| and max |v|
-        QREC_HIP_CHECK(hipMemsetAsync(v_max, 0, sizeof(float), st));
+        QREC_HIP_CHECK(hipMemsetAsync(w.v_max, 0, sizeof(float), st));
         const int v_rows_pad = g.n_item_tiles * 32;
-#define QREC_BF(LPR)                                                                                                                  \
-        hipLaunchKernelGGL((to_bf16_kernel<LPR, false>), dim3((unsigned)((g.b_pad + 4 * (64 / LPR) - 1) / (4 * (64 / LPR)))), dim3(256), 0, st, U,   \
-                           user_ids, n_b, g.b_pad, Ub, u_norm, (float *)nullptr);                                                     \
-        hipLaunchKernelGGL((to_bf16_kernel<LPR, true>), dim3((unsigned)((v_rows_pad + 4 * (64 / LPR) - 1) / (4 * (64 / LPR)))), dim3(256), 0, st, V, \
-                           (const int32_t *)nullptr, n_items, v_rows_pad, Vb, (float *)nullptr, v_max)
-        if (ld == 32) { QREC_BF(8); } else if (ld == 64) { QREC_BF(16); } else { QREC_BF(32); }
-#undef QREC_BF
+        with_nm_nu(ld, g.nu, [&](auto nm, auto) {
+            constexpr int LPR = 4 * nm(), rows = 4 * (64 / LPR);              // lanes per row (ld / 4), rows per block
+            hipLaunchKernelGGL((to_bf16_kernel<LPR, false>), dim3((unsigned)((g.b_pad + rows - 1) / rows)), dim3(256), 0, st, U,
+                               user_ids, n_b, g.b_pad, w.Ub, w.u_norm, (float *)nullptr);
+            hipLaunchKernelGGL((to_bf16_kernel<LPR, true>), dim3((unsigned)((v_rows_pad + rows - 1) / rows)), dim3(256), 0, st, V,
+                               (const int32_t *)nullptr, n_items, v_rows_pad, w.Vb, (float *)nullptr, w.v_max);
+        });
         QREC_LAUNCH_CHECK();
     }
     // (A) threshold: group maxima straight from a scoring loop -- fp32 over every kSampleStride-th item tile, or (bf16 route)
@@ -1754,31 +1764,28 @@ int run_fused_topk_f32(const float *U, const float *V, int d, int ld, int n_item
         if (waves > n_groups) waves = n_groups;
         if (waves < 1) waves = 1;
         const dim3 sgrid((unsigned)g.grid_x, (unsigned)((waves + 3) / 4));
-        int32_t *garg = reinterpret_cast<int32_t *>(base + g.off_garg);
-        if (use_bf16) {
-#define QREC_SM(NM, NU)                                                                                                               \
-            hipLaunchKernelGGL((sample_max_bf16_kernel<NM, NU>), sgrid, dim3(256), 0, st, Ub, Vb,                                      \
-                               n_items, n_b, g.b_pad, bf16_stride, n_s_tiles, tpg, n_groups, gmax, garg)
-            if (ld == 32) { QREC_SM(2, 4); }
-            else if (ld == 64) { if (g.nu == 2) { QREC_SM(4, 2); } else { QREC_SM(4, 4); } }
-            else { QREC_SM(8, 2); }
-#undef QREC_SM
-        } else if (ld <= 64)
-            hipLaunchKernelGGL(sample_max_kernel_f32<1>, sgrid, dim3(256), 0, st, U, V, ld, n_items, user_ids, n_b, g.b_pad, n_s_tiles, tpg, n_groups, gmax, garg);
+        if (use_bf16)
+            with_nm_nu(ld, g.nu, [&](auto nm, auto nu) {
+                hipLaunchKernelGGL((sample_max_bf16_kernel<nm(), nu()>), sgrid, dim3(256), 0, st, w.Ub, w.Vb, n_items, n_b, g.b_pad,
+                                   bf16_stride, n_s_tiles, tpg, n_groups, w.gmax, w.garg);
+            });
         else
-            hipLaunchKernelGGL(sample_max_kernel_f32<2>, sgrid, dim3(256), 0, st, U, V, ld, n_items, user_ids, n_b, g.b_pad, n_s_tiles, tpg, n_groups, gmax, garg);
+            with_nc(ld, [&](auto nc) {
+                hipLaunchKernelGGL(sample_max_kernel_f32<nc()>, sgrid, dim3(256), 0, st, U, V, ld, n_items, user_ids, n_b, g.b_pad, n_s_tiles,
+                                   tpg, n_groups, w.gmax, w.garg);
+            });
         QREC_LAUNCH_CHECK();
         const unsigned lane_blocks = (unsigned)((n_b + 255) / 256);
-        hipLaunchKernelGGL(threshold_var_kernel, dim3(lane_blocks), dim3(256), 0, st, gmax, garg, user_ids, rated_indptr, rated_sorted, g.b_pad, n_b,
-                           n_groups, M, tau);
+        hipLaunchKernelGGL(threshold_var_kernel, dim3(lane_blocks), dim3(256), 0, st, w.gmax, w.garg, user_ids, rated_indptr, rated_sorted, g.b_pad,
+                           n_b, n_groups, M, w.tau);
         QREC_LAUNCH_CHECK();
         if (use_bf16) {
-            hipLaunchKernelGGL(lowered_tau2_kernel, dim3(lane_blocks), dim3(256), 0, st, tau, u_norm, v_max, n_b, tau_low);
+            hipLaunchKernelGGL(lowered_tau2_kernel, dim3(lane_blocks), dim3(256), 0, st, w.tau, w.u_norm, w.v_max, n_b, w.tau_low);
             QREC_LAUNCH_CHECK();
         }
     }
     // (B) score + filter, (C) select
-    QREC_HIP_CHECK(hipMemsetAsync(n_flagged, 0, sizeof(int32_t), st));
+    QREC_HIP_CHECK(hipMemsetAsync(w.n_flagged, 0, sizeof(int32_t), st));
     // measured at the Yelp2018 shape (kernel time of this pass; 0.98 ms of pure MFMA time): one user tile per wavefront at 4
     // wavefronts per SIMD 2.49 ms (twice the operand loads per MFMA); two tiles at one wavefront per SIMD 1.72, at two
     // wavefronts per SIMD 1.67 (launched here); the item tile shared by a block's wavefronts through LDS (coalesced fetch,
@@ -1787,21 +1794,17 @@ int run_fused_topk_f32(const float *U, const float *V, int d, int ld, int n_item
     // tools/ubench/mfma_tile.hip; thresholds at +inf (no element ever appended) 1.66: the pass is bound by the per-lane-row
     // operand fetch interleaved with the accumulator read-out, not by the compare / append work
     const dim3 grid((unsigned)g.grid_x, (unsigned)g.grid_y);
-    if (use_bf16) {
+    if (use_bf16)
         // (B') the filter on v_mfma_f32_32x32x16_bf16 against the lowered thresholds
-#define QREC_BF(NM, NU)                                                                                                               \
-        hipLaunchKernelGGL((score_filter_bf16_kernel<NM, NU>), grid, dim3(256), 0, st, Ub, (int)g.b_pad, Vb, n_items, n_b, tau_low, g.n_lists,     \
-                           g.list_cap, cand_s, cand_i, cand_n)
-        if (ld == 32) { QREC_BF(2, 4); }
-        else if (ld == 64) { if (g.nu == 2) { QREC_BF(4, 2); } else { QREC_BF(4, 4); } }
-        else { QREC_BF(8, 2); }
-#undef QREC_BF
-    } else if (ld <= 64)
-        hipLaunchKernelGGL((score_filter2_kernel_f32<1, 2>), grid, dim3(256), 0, st, U, V, ld, n_items, user_ids, n_b, 0, tau, g.n_lists,
-                           cand_s, cand_i, cand_n);
+        with_nm_nu(ld, g.nu, [&](auto nm, auto nu) {
+            hipLaunchKernelGGL((score_filter_bf16_kernel<nm(), nu()>), grid, dim3(256), 0, st, w.Ub, (int)g.b_pad, w.Vb, n_items, n_b, w.tau_low,
+                               g.n_lists, g.list_cap, w.cand_s, w.cand_i, w.cand_n);
+        });
     else
-        hipLaunchKernelGGL((score_filter2_kernel_f32<2, 1>), grid, dim3(256), 0, st, U, V, ld, n_items, user_ids, n_b, 0, tau, g.n_lists,
-                           cand_s, cand_i, cand_n);
+        with_nc(ld, [&](auto nc) {                                // registers: two wavefronts per SIMD at one chunk, one at two
+            hipLaunchKernelGGL((score_filter2_kernel_f32<nc(), 2 / nc()>), grid, dim3(256), 0, st, U, V, ld, n_items, user_ids, n_b, 0, w.tau,
+                               g.n_lists, w.cand_s, w.cand_i, w.cand_n);
+        });
     QREC_LAUNCH_CHECK();
     // candidates per user: ~ (N + 1) * kSampleStride * 1.1, times ~1.4 behind the bf16 filter; the pool holds 4x that
     int pool_cap = g.n_lists * g.list_cap;
@@ -1810,33 +1813,24 @@ int run_fused_topk_f32(const float *U, const float *V, int d, int ld, int n_item
     const size_t lds = (size_t)kSelectWaves * pool_cap * sizeof(unsigned long long);
     const dim3 sgrid((unsigned)((n_b + kSelectWaves - 1) / kSelectWaves));
     const float *Ur = use_bf16 ? U : (const float *)nullptr;
-    if (ld <= 64) {
-        QREC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&select_topk_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(select_topk_kernel<1>, sgrid, dim3(64 * kSelectWaves), lds, st, cand_s, cand_i, cand_n, g.n_lists, tau, user_ids, rated_indptr,
-                           rated_sorted, n_b, K, ids_out, scores_out, flags, n_flagged, flagged_list, Ur, V, ld, pool_cap,
-                           reinterpret_cast<const float *>(base + g.off_taul), g.list_cap);
-    } else {
-        QREC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&select_topk_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(select_topk_kernel<2>, sgrid, dim3(64 * kSelectWaves), lds, st, cand_s, cand_i, cand_n, g.n_lists, tau, user_ids, rated_indptr,
-                           rated_sorted, n_b, K, ids_out, scores_out, flags, n_flagged, flagged_list, Ur, V, ld, pool_cap,
-                           reinterpret_cast<const float *>(base + g.off_taul), g.list_cap);
-    }
+    decltype(&select_topk_kernel<1>) select = nullptr;
+    with_nc(ld, [&](auto nc) { select = select_topk_kernel<nc()>; });
+    QREC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(select, sgrid, dim3(64 * kSelectWaves), lds, st, w.cand_s, w.cand_i, w.cand_n, g.n_lists, w.tau, user_ids, rated_indptr,
+                       rated_sorted, n_b, K, ids_out, scores_out, w.flags, w.n_flagged, w.flagged_list, Ur, V, ld, pool_cap, w.tau_low, g.list_cap);
     QREC_LAUNCH_CHECK();
     // (D) users whose heap history matters: the block path, fb_users at a time
     int32_t h_nf = 0;
-    QREC_HIP_CHECK(hipMemcpyAsync(&h_nf, n_flagged, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    QREC_HIP_CHECK(hipMemcpyAsync(&h_nf, w.n_flagged, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     QREC_HIP_CHECK(hipStreamSynchronize(st));
-    int32_t *fb_users = reinterpret_cast<int32_t *>(base + g.off_fbu), *fb_ids = reinterpret_cast<int32_t *>(base + g.off_fbi);
-    float *fb_sc = reinterpret_cast<float *>(base + g.off_fbs);
     // Their scores as USER-MAJOR rows ([user][item]: a step of the walk -- 64 consecutive items -- is one 256-B access), masked,
     // then the exact sequential emulation, one wavefront per user: three launches.  (History: through the whole block route --
     // sliced top-N, flags, exact_wave_kernel on an [item][b_pad] block, every load of a step its own cache line -- the fallback
     // was 0.8 ms of the evaluation's 3.05; as [panel][item][64] panels, a column striding 256 B, 0.18 ms for a handful of users.)
-    float *fb_block = reinterpret_cast<float *>(base + g.off_fb);
     const int64_t row_len = (int64_t)g.n_item_tiles * 32, panel = row_len * 64;
     for (int off = 0; off < h_nf; off += g.fb_users) {
         const int n = h_nf - off < g.fb_users ? h_nf - off : g.fb_users;
-        hipLaunchKernelGGL(gather_user_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, user_ids, flagged_list, off, n, fb_users);
+        hipLaunchKernelGGL(gather_user_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, user_ids, w.flagged_list, off, n, w.fb_users);
         QREC_LAUNCH_CHECK();
         const int n_utiles = (n + 63) / 64;
         int splits = (4096 + n_utiles - 1) / n_utiles;
@@ -1845,21 +1839,21 @@ int run_fused_topk_f32(const float *U, const float *V, int d, int ld, int n_item
         const int waves_per_utile = (g.n_item_tiles + per_wave - 1) / per_wave;
         // user-major rows (see score_kernel_f32): item stride 1, user stride row_len
         hipLaunchKernelGGL(score_kernel_f32, dim3((unsigned)n_utiles, (unsigned)((waves_per_utile + 3) / 4)), dim3(256), 0, st, U, V, ld,
-                           n_items, fb_users, n, 1, per_wave, fb_block, 1, panel, row_len);
+                           n_items, w.fb_users, n, 1, per_wave, w.fb_block, 1, panel, row_len);
         QREC_LAUNCH_CHECK();
         if (rated_indptr) {
-            hipLaunchKernelGGL(mask_kernel<float>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, fb_users, n, rated_indptr, rated_sorted,
-                               1, fb_block, 32, 1, panel, row_len);
+            hipLaunchKernelGGL(mask_kernel<float>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, w.fb_users, n, rated_indptr, rated_sorted,
+                               1, w.fb_block, 32, 1, panel, row_len);
             QREC_LAUNCH_CHECK();
         }
         {                                                         // fused route: K + 1 <= 64
             const int stage_items = n_items < kWalkChunk ? (n_items + 3) / 4 * 4 : kWalkChunk;
             const size_t walk_lds = (size_t)stage_items * sizeof(float);
             QREC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&exact_walk_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)walk_lds));
-            hipLaunchKernelGGL(exact_walk_lds_kernel, dim3((unsigned)n), dim3(256), walk_lds, st, fb_block, row_len, n_items, K, fb_ids, fb_sc);
+            hipLaunchKernelGGL(exact_walk_lds_kernel, dim3((unsigned)n), dim3(256), walk_lds, st, w.fb_block, row_len, n_items, K, w.fb_ids, w.fb_sc);
         }
         QREC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)((n * K + 255) / 256)), dim3(256), 0, st, flagged_list, off, n, K, fb_ids, fb_sc,
+        hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)((n * K + 255) / 256)), dim3(256), 0, st, w.flagged_list, off, n, K, w.fb_ids, w.fb_sc,
                            ids_out, scores_out);
         QREC_LAUNCH_CHECK();
     }
@@ -1885,12 +1879,7 @@ __global__ __launch_bounds__(256) void rank_hits_kernel(const int32_t *__restric
     for (int pos = 0; pos < n_cut; pos++) {
         const int item = ids[(int64_t)b * row_stride + pos];
         if (item < 0) break;                       // -1 padding: fewer than N items exist
-        int64_t lo = lo0, hi = hi0;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (test_items[mid] < item) lo = mid + 1; else hi = mid;
-        }
-        if (lo < hi0 && test_items[lo] == item) { hits++; dcg += discount[pos]; }
+        if (sorted_find(test_items + lo0, hi0 - lo0, item) >= 0) { hits++; dcg += discount[pos]; }
     }
     hits_out[b] = hits;
     dcg_out[b] = dcg;
@@ -1905,11 +1894,11 @@ int qrec_score_topk_scratch_bytes(int dtype, int32_t n_items, int32_t n_batch_us
     QREC_REQUIRE(dtype == QREC_F32 || dtype == QREC_F64, "qrec_score_topk_scratch_bytes: bad dtype %d", dtype);
     if (fused_ok(dtype, ld, n_items, K) && n_batch_users > 0) {
         // fused path: the sampled block (1/8), candidate lists, and a block-path scratch for the flagged users' rounds
-        *bytes = (int64_t)fused_geometry(n_items, n_batch_users, ld).total;
+        *bytes = layout_bytes(fused_layout, fused_geometry(n_items, n_batch_users, ld), n_items, ld);
         return QREC_OK;
     }
     // the transposed score block, then the sliced top-N's candidates (scores + ids), flags, flagged list, counter
-    *bytes = (int64_t)block_path_bytes(dtype == QREC_F64 ? 8 : 4, n_items, n_batch_users);
+    *bytes = dtype == QREC_F64 ? block_path_bytes<double>(n_items, n_batch_users) : block_path_bytes<float>(n_items, n_batch_users);
     return QREC_OK;
 }
 
@@ -1938,7 +1927,7 @@ int qrec_score_topk(const void *d_U, const void *d_V, int dtype, int32_t d, int3
 
 int qrec_score_topk_sigmoid_bias_scratch_bytes(int32_t n_items, int32_t n_batch_users, int64_t *bytes) {
     QREC_REQUIRE(bytes && n_items >= 0 && n_batch_users >= 0, "qrec_score_topk_sigmoid_bias_scratch_bytes: bad arguments");
-    *bytes = (int64_t)block_path_bytes(4, n_items, n_batch_users);
+    *bytes = block_path_bytes<float>(n_items, n_batch_users);
     return QREC_OK;
 }
 
@@ -1958,7 +1947,7 @@ int qrec_score_topk_sigmoid_bias(const float *d_U, const float *d_V, const float
 
 int qrec_score_topk_sparse_row_sigmoid_bias_scratch_bytes(int32_t n_items, int32_t n_batch_users, int64_t *bytes) {
     QREC_REQUIRE(bytes && n_items >= 0 && n_batch_users >= 0, "qrec_score_topk_sparse_row_sigmoid_bias_scratch_bytes: bad arguments");
-    *bytes = (int64_t)block_path_bytes(4, n_items, n_batch_users);
+    *bytes = block_path_bytes<float>(n_items, n_batch_users);
     return QREC_OK;
 }
 

@@ -190,3 +190,98 @@ def test_channel_attention_bwd_stays_inside_its_stated_scratch():
         res.update(dh=dh.numpy(), g_att=g_a.numpy(), g_att_mat=g_M.numpy())
         return res
     _twice("MHCN channel attention backward rows=300 ld=32", 4 * capi.channel_attention_scratch_floats(), run)
+
+
+# ---- evaluation (csrc/eval_topk.hip): the block layout and the fused layout ------------------------------------------------------------
+def _ranked_inside(what, rk, users, N):
+    """the ranker's one call for `users` in a scratch of exactly the bytes the library states for it"""
+    from qrec_amd.capi import DeviceBuffer as DB
+    n = users.size
+
+    def run(ws):
+        rk._scratch, rk._d_ids, rk._d_sc, rk._cap = ws, DB.zeros((n, N), np.int32), DB.zeros((n, N), rk.dtype), (n, N)
+        ids, sc = rk.topk(users, N)
+        assert rk._scratch is ws
+        return dict(ids=ids, scores=sc)
+    _twice(what, rk._scratch_bytes(n, N), run)
+
+
+def test_heap_only_evaluation_stays_inside_its_stated_scratch():
+    """fp64, 129 users x 257 items: below 8,192 items only the score block of the block layout is touched"""
+    from qrec_amd.interactions import user_item_csr
+    from qrec_amd.ranking import DeviceRanker
+    rng = np.random.default_rng(129)
+    nu, ni, d, N = 129, 257, 50, 20
+    U, V = rng.standard_normal((nu, d)), rng.standard_normal((ni, d))
+    rated = user_item_csr(rng.integers(0, nu, 4 * nu), rng.integers(0, ni, 4 * nu), np.ones(4 * nu), nu, ni)
+    _ranked_inside("evaluation fp64 129x257", DeviceRanker(U, V, rated), rng.permutation(nu).astype(np.int32), N)
+
+
+def test_sliced_evaluation_stays_inside_its_stated_scratch():
+    """fp32, 96 users x 8,200 items, tables as tests/test_gpu_eval.py::test_sliced_topk_and_its_exact_fallbacks builds them (user k
+    is the k-th unit vector): 7 users tie inside their N + 1 best, are flagged by the merge and redone by the exact wavefront
+    kernel -- flags, the flagged list and its counter, the last arrays of the block layout, are written and read"""
+    from qrec_amd.interactions import user_item_csr
+    from qrec_amd.ranking import DeviceRanker
+    rng = np.random.default_rng(8200)
+    nu, ni, N = 96, 8200, 20
+    V = np.empty((ni, nu), np.float32)
+    for k in range(nu):
+        V[:, k] = rng.permutation(ni) - ni // 3
+    for k in rng.permutation(nu)[:7]:
+        V[:, k] = rng.integers(-5, 40, ni)
+    rated = user_item_csr(rng.integers(0, nu, 500), rng.integers(0, ni, 500), np.ones(500), nu, ni)
+    _ranked_inside("evaluation fp32 96x8200, sliced", DeviceRanker(np.eye(nu, dtype=np.float32), V, rated), rng.permutation(nu).astype(np.int32), N)
+
+
+@pytest.mark.parametrize("route", ["bf16", "f32-filter", "bf16-two-tiles"])
+def test_fused_evaluation_stays_inside_its_stated_scratch(route, monkeypatch):
+    """fp32, d = 64, 65 users (one past user padding) x 16,417 items (past the fused boundary, ragged last tile), tables as
+    tests/test_gpu_eval.py::test_fused_route_equals_the_block_route builds them: users whose scores are all negative or all 0
+    and duplicated popular items flag users, so stage (D) writes the fallback region at the layout's end"""
+    from qrec_amd.interactions import user_item_csr
+    from qrec_amd.ranking import DeviceRanker
+    for k, v in {"bf16": {}, "f32-filter": {"QREC_EVAL_F32_FILTER": "1"}, "bf16-two-tiles": {"QREC_EVAL_NU": "2"}}[route].items():
+        monkeypatch.setenv(k, v)
+    rng = np.random.default_rng(16417)
+    nu, ni, d, N = 80, 16384 + 33, 64, 20
+    pop = (np.arange(ni, dtype=np.float64) + 1) ** -0.5
+    V = (rng.standard_normal((ni, d)) * 0.3 + pop[:, None] * 2.0).astype(np.float32)
+    U = (rng.standard_normal((nu, d)) * 0.3 + 0.5).astype(np.float32)
+    U[::7] = -np.abs(U[::7])
+    U[3::50] = 0.0
+    V[5000:5040] = V[100:140]
+    uu = rng.integers(0, nu, 30 * nu); ii = (rng.integers(0, ni, 30 * nu) ** 2 // ni).astype(np.int64)
+    rated = user_item_csr(uu, ii, np.ones(uu.size), nu, ni)
+    _ranked_inside(f"evaluation fp32 65x16417, fused {route}", DeviceRanker(U, V, rated), rng.permutation(nu)[:65].astype(np.int32), N)
+
+
+def _rated_with_values(rng, nu, ni, per_user):
+    from qrec_amd.interactions import CSR
+    iid = np.concatenate([np.sort(rng.permutation(ni)[:per_user]) for _ in range(nu)]).astype(np.int32)
+    return CSR(np.arange(nu + 1, dtype=np.int64) * per_user, iid, rng.integers(1, 9, iid.size) / 2)
+
+
+def test_sigmoid_bias_evaluation_stays_inside_its_stated_scratch():
+    """40 users x 1,003 items, 24 hidden units at stride 32: the shape of tests/test_gpu_cdae.py's ranker"""
+    from qrec_amd.capi import DeviceBuffer as DB
+    from qrec_amd.ranking import SigmoidBiasRanker
+    rng = np.random.default_rng(1003)
+    nu, ni, nh = 40, 1003, 24
+    H, W = (pad_cols(rng.uniform(-0.5, 0.5, (r, nh)).astype(np.float32), LD) for r in (nu, ni))
+    b = rng.uniform(-1.0, 1.0, ni).astype(np.float32)
+    rk = SigmoidBiasRanker(DB.from_numpy(H), DB.from_numpy(W), DB.from_numpy(b), nu, ni, nh, LD, _rated_with_values(rng, nu, ni, 30))
+    _ranked_inside("sigmoid-bias evaluation 40x1003", rk, rng.permutation(nu).astype(np.int32), 10)
+
+
+def test_sparse_row_sigmoid_bias_evaluation_stays_inside_its_stated_scratch():
+    """73 users x 477 items at stride 480: the shape of tests/test_gpu_cfgan.py's ranker"""
+    from qrec_amd.capi import DeviceBuffer as DB
+    from qrec_amd.ranking import SparseRowSigmoidRanker
+    rng = np.random.default_rng(477)
+    nu, ni = 73, 477
+    ld = -(-ni // 32) * 32
+    W = pad_cols(rng.uniform(-0.2, 0.2, (ni, ni)).astype(np.float32), ld)
+    b = pad_cols(rng.uniform(-1.0, 1.0, (1, ni)).astype(np.float32), ld)[0]
+    rk = SparseRowSigmoidRanker(DB.from_numpy(W), DB.from_numpy(b), nu, ni, ld, _rated_with_values(rng, nu, ni, 20))
+    _ranked_inside("sparse-row sigmoid-bias evaluation 73x477", rk, rng.permutation(nu).astype(np.int32), 12)
