@@ -9,9 +9,9 @@ from __future__ import annotations
 import numpy as np
 
 from . import capi
-from . import graph as _g
 from .capi import DeviceBuffer, DeviceSlice
 from .engine import padded_ld
+from .optim import Adam, AdamClock
 
 NEGATIVES_PER_RATED = 5          # CDAE.py:53
 
@@ -199,8 +199,8 @@ class CdaeTrainer:
         Vp = np.zeros((nu, ld), np.float32); Vp[:, :nh] = V
         self.V = DeviceBuffer.from_numpy(Vp)
         self.gV = DeviceBuffer.zeros((nu, ld), np.float32)
-        self.opt = _g._Adam(self.theta, lr)
-        self.optV = _g._Adam(self.V, lr)
+        self.opt = Adam(self.theta, lr)
+        self.optV = Adam(self.V, lr)
         self.d_loss = DeviceBuffer.zeros(1, np.float64)
         self._B = 0
         self._stage = None
@@ -352,9 +352,7 @@ class CfganTrainer:
         z = lambda a: DeviceBuffer.zeros(a.shape, np.float32)
         self.mW, self.vW, self.mb, self.vb, self.mD, self.vD = z(W), z(W), z(b), z(b), z(tD), z(tD)
         self.gW, self.gb, self.gD = (z(W), z(b), z(tD)) if keep_gradients else (None, None, None)
-        f = np.float32
-        self._b1, self._b2, self._eps = f(0.9), f(0.999), f(1e-8)
-        self._pow = {"D": [self._b1, self._b2], "G": [self._b1, self._b2]}          # beta powers, advanced after each step of that optimizer
+        self.optD, self.optG = AdamClock(lr), AdamClock(lr)      # the updates themselves run inside the step kernels
         self.losses = DeviceBuffer.zeros(8, np.float64)     # (D_loss, G_loss) of the forward pass of the D step and of the three G steps
         self._loss_at = [DeviceSlice(self.losses, 2 * k, (2,)) for k in range(4)]
         self._g_steps = 0
@@ -368,13 +366,6 @@ class CfganTrainer:
         if B > self._B or n_live > self._slots:
             self._B, self._slots = max(B, self._B), max(max(n_live, 1) * 5 // 4 + 64, self._slots)
             self.ws = DeviceBuffer(capi.cfgan_workspace_bytes(self._B, self._slots), np.uint8)
-
-    def _adam_alpha(self, which: str) -> float:
-        f = np.float32
-        b1p, b2p = self._pow[which]
-        alpha = float(f(f(self.lr) * np.sqrt(f(1) - b2p, dtype=f) / (f(1) - b1p)))
-        self._pow[which] = [f(b1p * self._b1), f(b2p * self._b2)]
-        return alpha
 
     def _prepare(self, lists: BatchLists, stream) -> BatchLists:
         if lists.n_items != self.ni:
@@ -392,15 +383,18 @@ class CfganTrainer:
 
     def dis_step_async(self, lists: BatchLists, stream=None) -> BatchLists:
         L = self.forward(lists, stream, 0)
-        capi.cfgan_dis_step(self.thetaD, self.mD, self.vD, self.ni, L, self.ws, self._adam_alpha("D"), float(self._b1), float(self._b2),
-                            float(self._eps), self.gD, stream)
+        o = self.optD
+        alpha = o.alpha(); o.advance()
+        capi.cfgan_dis_step(self.thetaD, self.mD, self.vD, self.ni, L, self.ws, alpha, float(o.b1), float(o.b2), float(o.eps), self.gD, stream)
         self._g_steps = 0
         return L
 
     def gen_step_async(self, lists: BatchLists, stream=None) -> BatchLists:
         L = self.forward(lists, stream, 1 + self._g_steps % 3)
-        capi.cfgan_gen_sweep(self.W, self.mW, self.vW, self.b, self.mb, self.vb, self.ni, self.ld, L, self.ws, self._adam_alpha("G"),
-                             float(self._b1), float(self._b2), float(self._eps), self.gW, self.gb, stream)
+        o = self.optG
+        alpha = o.alpha(); o.advance()
+        capi.cfgan_gen_sweep(self.W, self.mW, self.vW, self.b, self.mb, self.vb, self.ni, self.ld, L, self.ws, alpha,
+                             float(o.b1), float(o.b2), float(o.eps), self.gW, self.gb, stream)
         self._g_steps += 1
         return L
 

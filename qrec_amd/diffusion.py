@@ -8,6 +8,7 @@ from . import capi
 from . import graph as _g
 from .capi import DeviceBuffer, DeviceSlice
 from .engine import padded_ld
+from .optim import Adam
 
 
 def _csr(M):
@@ -81,7 +82,7 @@ class DiffNetTrainer:
     flows back through every layer; the weights are not regularised.  Adam on [U; V] (one launch) and on all W_k (one launch)."""
 
     def __init__(self, U0, V0, W, S_csr, A_csr, lr: float, reg: float, n_layers: int):
-        self.ows = _g._ordered_ws()      # parity mode (ordered_reductions()): ordered gradient scatter; None = float atomics
+        self.ows = _g._ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n, self.L = self.nu + self.ni, int(n_layers)
         if len(W) != self.L:
@@ -93,9 +94,7 @@ class DiffNetTrainer:
         nu, ni, d = self.nu, self.ni, self.d
         self.plan_S = _g.SpmmPlan(*_csr(S_csr), ld); self.plan_St = _g.SpmmPlan(*_csr(S_csr.T), ld)
         self.plan_A = _g.SpmmPlan(*_csr(A_csr), ld); self.plan_At = _g.SpmmPlan(*_csr(A_csr.T), ld)
-        E0 = np.zeros((self.n, ld), np.float32)
-        E0[:nu, :d] = U0; E0[nu:, :d] = V0
-        self.E = DeviceBuffer.from_numpy(E0)                       # [U; V], the parameters
+        self.E = DeviceBuffer.from_numpy(_g.pack_joint(U0, V0, ld))   # [U; V], the parameters
         self.Eu, self.Ev = DeviceSlice(self.E, 0, (nu, ld)), DeviceSlice(self.E, nu * ld, (ni, ld))
         zu = lambda: DeviceBuffer.zeros((nu, ld), np.float32)
         self.u = [self.Eu] + [zu() for _ in range(self.L)]         # u_0 (= U), u_1 .. u_L
@@ -117,8 +116,8 @@ class DiffNetTrainer:
         self.W = [DeviceSlice(self.W_all, k * ll, (2, ld, ld)) for k in range(self.L)]
         self.gW = [DeviceSlice(self.gW_all, k * ll, (2, ld, ld)) for k in range(self.L)]
         self.ws = DeviceBuffer(capi.dense_layer_ws_bytes(nu, ld, 2), np.uint8)
-        self.optE = _g._Adam(self.E, lr)
-        self.optW = _g._Adam(self.W_all, lr) if self.L else None
+        self.optE = Adam(self.E, lr)
+        self.optW = Adam(self.W_all, lr) if self.L else None
         self.d_loss = DeviceBuffer.zeros(1, np.float64)
         self.loss_slots = _ordered_loss_slots(self.ows)
 
@@ -163,19 +162,16 @@ class DiffNetTrainer:
 
     def parameters(self):
         """(U, V, [W_k (2d x d)])"""
-        E = self.E.numpy()[:, :self.d]
-        return E[:self.nu].copy(), E[self.nu:].copy(), self._weights(self.W_all)
+        return (*_g.split_joint(self.E.numpy(), self.nu, self.d), self._weights(self.W_all))
 
     def gradients(self):
         """(dU, dV, [dW_k]) of the last step, before Adam"""
-        g = self.optE.applied_gradient()[:, :self.d]
-        return g[:self.nu], g[self.nu:], self._weights(self.gW_all)
+        return (*_g.split_joint(self.optE.applied_gradient(), self.nu, self.d), self._weights(self.gW_all))
 
     def inference_embeddings(self):
         """(u_final, V): the tables DiffNet.py:57 scores with"""
         self.forward()
-        F = self.F.numpy()[:, :self.d]
-        return np.ascontiguousarray(F[:self.nu]), np.ascontiguousarray(F[self.nu:])
+        return _g.split_joint(self.F.numpy(), self.nu, self.d)
 
 
 class DHCFTrainer:
@@ -204,10 +200,8 @@ class DHCFTrainer:
         self.lr, self.reg, self.seed = lr, reg, seed
         P, Q = dhcf_factor_graphs(self.nu, self.ni, uid, iid)
         self.plan_P = _g.SpmmPlan(*_csr(P), ld, split_row=self.nu); self.plan_Q = _g.SpmmPlan(*_csr(Q), ld, split_row=self.nu)
-        E0 = np.zeros((n, ld), np.float32)
-        E0[:self.nu, :self.d] = U0; E0[self.nu:, :self.d] = V0
         z = lambda: DeviceBuffer.zeros((n, ld), np.float32)
-        self.Z = [DeviceBuffer.from_numpy(E0), z(), z()]           # E_0 (parameters), z_1, z_2: each layer's residual input / output
+        self.Z = [DeviceBuffer.from_numpy(_g.pack_joint(U0, V0, ld)), z(), z()]          # E_0 (parameters), z_1, z_2: each layer's residual input / output
         self.T, self.side, self.nxt = z(), z(), z()
         self.gate = [z(), z()]
         self.inv = [DeviceBuffer.zeros(n, np.float32), DeviceBuffer.zeros(n, np.float32)]
@@ -221,8 +215,8 @@ class DHCFTrainer:
         self.W = [DeviceSlice(self.W_all, k * ld * ld, (ld, ld)) for k in range(2)]
         self.gW = [DeviceSlice(self.gW_all, k * ld * ld, (ld, ld)) for k in range(2)]
         self.ws = DeviceBuffer(capi.dense_layer_ws_bytes(n, ld, 1), np.uint8)
-        self.optE = _g._Adam(self.Z[0], lr)
-        self.optW = _g._Adam(self.W_all, lr)
+        self.optE = Adam(self.Z[0], lr)
+        self.optW = Adam(self.W_all, lr)
         self.d_loss = DeviceBuffer.zeros(1, np.float64)
         self.loss_slots = _ordered_loss_slots(self.ows)
         self.step_no = 0
@@ -273,17 +267,14 @@ class DHCFTrainer:
 
     def parameters(self):
         """(U, V, [W_1, W_2])"""
-        E = self.Z[0].numpy()[:, :self.d]
-        return E[:self.nu].copy(), E[self.nu:].copy(), [w.numpy()[:self.d, :self.d].copy() for w in self.W]
+        return (*_g.split_joint(self.Z[0].numpy(), self.nu, self.d), [w.numpy()[:self.d, :self.d].copy() for w in self.W])
 
     def gradients(self):
         """(dU, dV, [dW_1, dW_2]) of the last step as minimize() applied them, before Adam"""
-        g = self.optE.applied_gradient()[:, :self.d]
         gw = self.optW.applied_gradient(self.W_prev.numpy())
-        return g[:self.nu], g[self.nu:], [gw[k, :self.d, :self.d] for k in range(2)]
+        return (*_g.split_joint(self.optE.applied_gradient(), self.nu, self.d), [gw[k, :self.d, :self.d] for k in range(2)])
 
     def inference_embeddings(self):
         """3d-wide (U, V) of the inference graph (isTraining = 0, DHCF.py:123-127)"""
         self.forward(False)
-        A = self.All.numpy()[:, :self.wide_d]
-        return np.ascontiguousarray(A[:self.nu]), np.ascontiguousarray(A[self.nu:])
+        return _g.split_joint(self.All.numpy(), self.nu, self.wide_d)

@@ -12,28 +12,12 @@ import numpy as np
 from . import capi
 from .capi import DeviceBuffer, DeviceSlice
 from .engine import padded_ld
+from .optim import AdamClock
 
 TEMPERATURE = 0.2          # IRGAN.py:88
 SAMPLE_LAMBDA = 0.2        # IRGAN.py:143
 NEG_PER_POS, GEN_PER_POS = 2, 3
 ROW_SCRATCH_BYTES = 256 << 20      # get_data's block of users is sized so that its three [B][n_items] float rows stay below this
-
-
-class _BetaPowers:
-    """the host side of one tf.train.AdamOptimizer: fp32 beta powers, multiplied once per step after the update"""
-
-    def __init__(self, lr: float):
-        f = np.float32
-        self.lr, self.b1, self.b2, self.eps = f(lr), f(0.9), f(0.999), f(1e-8)
-        self.b1p, self.b2p = self.b1, self.b2
-
-    def alpha(self) -> float:
-        f = np.float32
-        return float(f(self.lr * np.sqrt(f(1) - self.b2p, dtype=f) / (f(1) - self.b1p)))
-
-    def advance(self):
-        f = np.float32
-        self.b1p = f(self.b1p * self.b1); self.b2p = f(self.b2p * self.b2)
 
 
 class _Tower:
@@ -75,7 +59,7 @@ class IrganTrainer:
         self.lr, self.reg, self.seed = float(lr), float(reg), int(seed)
         self.gen, self.dis = _Tower(a["g_P"], a["g_Q"], a["g_b"], self.d, self.ld), _Tower(a["d_P"], a["d_Q"], a["d_b"], self.d, self.ld)
         self.dis.gQ = DeviceBuffer.zeros((self.ni, self.ld), np.float32)
-        self.gen_opt, self.dis_opt = _BetaPowers(lr), _BetaPowers(lr)
+        self.gen_opt, self.dis_opt = AdamClock(lr), AdamClock(lr)
         self.d_pos = (DeviceBuffer.from_numpy(indptr), DeviceBuffer.from_numpy(items if items.size else np.zeros(1, np.int32)))
         self.d_user_ids = DeviceBuffer.from_numpy(np.arange(self.nu, dtype=np.int32))
         gen_ptr = np.zeros((self.nu, 2), np.int64); gen_ptr[:, 1] = GEN_PER_POS * self.n_pos

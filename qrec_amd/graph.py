@@ -12,6 +12,7 @@ import numpy as np
 from . import capi
 from .capi import DeviceBuffer
 from .engine import padded_ld
+from .optim import Adam
 
 # ---- reduction order of the batch-gradient scatters ------------------------------------------------------------------------
 # Throughput mode adds a batch's row gradients into the table gradient with float atomics (right to fp32 rounding; the order,
@@ -33,7 +34,27 @@ def ordered_reductions(on: bool = True):
 
 
 def _ordered_ws():
+    """what a trainer keeps as ``self.ows``: in parity mode (``ordered_reductions()``) the workspace of the ordered gradient
+    scatters, otherwise None = float atomics"""
     return capi.OrderedScatter() if getattr(_REDUCTIONS, "ordered", False) else None
+
+
+def pack_joint(U0, V0, ld: int) -> np.ndarray:
+    """[U0; V0] as one host float32 table of row stride ``ld``, pad columns zero: how every graph trainer keeps E = [U; V]"""
+    nu, d = np.shape(U0)
+    E0 = np.zeros((nu + np.shape(V0)[0], ld), np.float32)
+    E0[:nu, :d] = U0; E0[nu:, :d] = V0
+    return E0
+
+
+def split_joint(A: np.ndarray, nu: int, d: int):
+    """(users, items) of a joint host table: rows [0, nu) and [nu, n), the first ``d`` columns, as contiguous copies"""
+    return A[:nu, :d].copy(), A[nu:, :d].copy()
+
+
+def _row_subset(subset, bound: int):
+    """the ``capi.RowSubset`` of a step's batch rows, grown on demand: ``subset`` itself while it holds ``bound`` rows"""
+    return subset if subset is not None and subset.capacity >= bound else capi.RowSubset(bound)
 
 
 def joint_norm_adjacency(n_users: int, n_items: int, uid: np.ndarray, iid: np.ndarray):
@@ -304,24 +325,20 @@ class LightGCNTrainer:
 
     def __init__(self, U0: np.ndarray, V0: np.ndarray, adj, n_layers: int, lr: float, reg: float,
                  loss_eps: float = 1e-7):
-        self.ows = _ordered_ws()      # parity mode (ordered_reductions()): workspace of the ordered gradient scatters; None = float atomics
+        self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni
         self.ld = padded_ld(self.d, np.float32)
         self.L, self.lr, self.reg, self.loss_eps = n_layers, lr, reg, loss_eps
         self.plan = SpmmPlan(adj[0], adj[1], adj[2], self.ld, split_row=self.nu)
-        E0 = np.zeros((self.n, self.ld), np.float32)
-        E0[:self.nu, :self.d] = U0; E0[self.nu:, :self.d] = V0
-        self.E = DeviceBuffer.from_numpy(E0)
+        self.E = DeviceBuffer.from_numpy(pack_joint(U0, V0, self.ld))
+        self.opt = Adam(self.E, lr)
         z = lambda: DeviceBuffer.zeros((self.n, self.ld), np.float32)
-        self.m, self.v, self.S, self.dE, self.A, self.B = z(), z(), z(), z(), z(), z()
+        self.S, self.dE, self.A, self.B = z(), z(), z(), z()
         self.d_loss = DeviceBuffer.zeros(1, np.float64)
         self.row_mask = DeviceBuffer.zeros((self.n + 31) // 32, np.uint32)   # non-zero rows of the batch gradient
         self.batch_rows = None  # capi.RowSubset: the same rows as a list
         self.t = 0
-        f = np.float32
-        self.b1, self.b2, self.adam_eps = f(0.9), f(0.999), f(1e-8)
-        self.b1p, self.b2p = self.b1, self.b2          # fp32 beta powers, as TF keeps them
         self.dp = None                                  # dist.BatchParallel: this rank trains a share of every step's rows
 
     # ---- pieces -----------------------------------------------------------------------------
@@ -349,17 +366,11 @@ class LightGCNTrainer:
             x = y
         return x
 
-    def adam_alpha(self) -> float:
-        """lr * sqrt(1 - beta2_power) / (1 - beta1_power), evaluated in fp32 (TF ApplyAdam)."""
-        f = np.float32
-        return float(f(f(self.lr) * np.sqrt(f(1) - self.b2p, dtype=f) / (f(1) - self.b1p)))
-
     def train_step_async(self, d_u, d_i, d_j, B: int, stream=None):
         """u/i/j: device pointers (int32[B]); enqueue only, read the loss with ``loss()``."""
         # one launch: the bitmap of the rows {u, nu+i, nu+j} of the batch, cleared first, and the loss accumulator cleared
         bound = min(3 * B, self.n)
-        if self.batch_rows is None or self.batch_rows.capacity < bound:
-            self.batch_rows = capi.RowSubset(bound)
+        self.batch_rows = _row_subset(self.batch_rows, bound)
         subset = capi.mark_compact_batch_rows(d_u, d_i, d_j, B, self.nu, self.n, self.row_mask, self.batch_rows, bound, stream,
                                               d_zero8=self.d_loss, n_zero8=1)
         self.forward_sum(stream, last_rows=self.row_mask)
@@ -375,57 +386,78 @@ class LightGCNTrainer:
         g = self.backward_from_dE(stream)
         if self.dp is not None:        # the step's gradient and loss = sums over the ranks' shares of its rows
             self.dp.all_reduce(g); self.dp.all_reduce(self.d_loss)
-        capi.adam_step(self.E, self.m, self.v, g, self.n * self.ld, 1.0 / (self.L + 1), self.adam_alpha(),
-                       float(self.b1), float(self.b2), float(self.adam_eps), stream)
-        self.last_grad = (g, 1.0 / (self.L + 1), 0.0)
+        self.opt.step(g, 1.0 / (self.L + 1), stream)
         self.t += 1
-        self.b1p = np.float32(self.b1p * self.b1); self.b2p = np.float32(self.b2p * self.b2)
 
     def loss(self, stream=None) -> float:
         return float(self.d_loss.numpy(stream)[0])
 
     def gradients(self):
         """the last step's gradient of (U, V) as the reference's minimize() applies it (before Adam)"""
-        g = _applied_gradient(self.last_grad)[:, :self.d]
-        return g[:self.nu], g[self.nu:]
+        return split_joint(self.opt.applied_gradient(), self.nu, self.d)
 
     def final_embeddings(self):
         """(U, V) = split(mean(E0..EL)) as float32 host arrays (LightGCN.py:41)."""
         self.forward_sum()
-        Ebar = (self.S.numpy()[:, :self.d] / np.float32(self.L + 1)).astype(np.float32)
-        return np.ascontiguousarray(Ebar[:self.nu]), np.ascontiguousarray(Ebar[self.nu:])
+        return split_joint((self.S.numpy()[:, :self.d] / np.float32(self.L + 1)).astype(np.float32), self.nu, self.d)
 
     def ego_embeddings(self):
-        E = self.E.numpy()
-        return E[:self.nu, :self.d].copy(), E[self.nu:, :self.d].copy()
+        return split_joint(self.E.numpy(), self.nu, self.d)
 
 
-def _setup_row_exchange(tr, adj, blk_ptr, sel):
-    """How a row-partitioned trainer gets the operand rows of a propagation product (env QREC_GRAPH_EXCHANGE):
+class _RowPartitioned:
+    """What the row-partitioned trainers share: rank r owns the contiguous rows [lo, hi) of the joint adjacency and of every
+    node table (``dist.RowPartition``), padded to ``rows_pad`` rows per rank.
+
+    How a propagation product gets its operand rows (env QREC_GRAPH_EXCHANGE):
     ``allgather`` (default): every rank receives every block, N x ld floats per product and rank;
     ``referenced`` (round 3; SURVEY s8e "all-to-all of only referenced remote rows"): a rank receives the distinct remote rows its
     block of the adjacency refers to -- worked out once per graph (dist.RowPartition.reference), one row gather + one row
     all-to-all per product into a compact operand whose column numbering the block's CSR is rewritten to.  Same products,
     same bits; fewer bytes where the graph has locality (DESIGN.md s7 has both synthetic graphs)."""
-    tr.exchange = os.environ.get("QREC_GRAPH_EXCHANGE", "allgather")
-    if tr.exchange not in ("allgather", "referenced"):
-        raise ValueError("QREC_GRAPH_EXCHANGE must be allgather or referenced")
-    if tr.exchange == "referenced":
-        cols = tr.rp.reference(adj[0], adj[1])
-        tr.plan_ref = SpmmPlan(blk_ptr, cols, adj[2][sel], tr.ld)
-        tr.X_ref = DeviceBuffer.zeros((tr.rp.ref_rows, tr.ld), np.float32)
+
+    def _init_rows(self, comm, adj, E0: np.ndarray) -> np.ndarray:
+        """needs ``self.n`` and ``self.ld``.  Sets ``comm``, ``rp``, ``plan`` (rows = this rank's block of the adjacency, pad rows
+        empty, columns global), the exchange (``exchange``, ``plan_ref``, ``X_ref``) and the whole-height operand ``X_full``;
+        returns this rank's rows of the host table ``E0``, zero-padded to ``rows_pad`` rows."""
+        from .dist import RowPartition
+        self.comm = comm
+        rp = self.rp = RowPartition(comm, self.n, self.ld)
+        lo, hi, pad = rp.lo, rp.hi, rp.rows_pad
+        indptr, indices, values = adj
+        blk_ptr = (indptr[lo:hi + 1] - indptr[lo]).astype(np.int64)
+        blk_ptr = np.concatenate([blk_ptr, np.full(pad - (hi - lo), blk_ptr[-1] if hi > lo else 0, np.int64)])
+        sel = slice(int(indptr[lo]), int(indptr[hi]))
+        self.plan = SpmmPlan(blk_ptr, indices[sel], values[sel], self.ld)
+        self.exchange = os.environ.get("QREC_GRAPH_EXCHANGE", "allgather")
+        if self.exchange not in ("allgather", "referenced"):
+            raise ValueError("QREC_GRAPH_EXCHANGE must be allgather or referenced")
+        self.plan_ref = self.X_ref = None
+        if self.exchange == "referenced":
+            self.plan_ref = SpmmPlan(blk_ptr, rp.reference(indptr, indices), values[sel], self.ld)
+            self.X_ref = DeviceBuffer.zeros((rp.ref_rows, self.ld), np.float32)
+        self.X_full = self._full()
+        blk = np.zeros((pad, self.ld), np.float32); blk[:hi - lo] = E0[lo:hi]
+        return blk
+
+    def _full(self, ld: int | None = None) -> DeviceBuffer:
+        """a zeroed table over the rows of ALL ranks' padded blocks"""
+        return DeviceBuffer.zeros((self.rp.world * self.rp.rows_pad, ld or self.ld), np.float32)
+
+    def _row_operand(self, x, stream):
+        """(plan, operand) for  y = A_hat[lo:hi] X  with this rank's block ``x`` of X: the exchange of the operand rows goes out here"""
+        if self.exchange == "referenced":
+            self.rp.gather_referenced(x, self.X_ref, stream)
+            return self.plan_ref, self.X_ref
+        self.rp.gather_operand(x, self.X_full, stream)
+        return self.plan, self.X_full
+
+    def block(self, buf) -> np.ndarray:
+        """this rank's rows of a block buffer (pad rows and pad columns dropped)"""
+        return buf.numpy()[:self.rp.hi - self.rp.lo, :self.d].copy()
 
 
-def _row_operand(tr, x, stream):
-    """(plan, operand) for  y = A_hat[lo:hi] X  with this rank's block ``x`` of X: the exchange of the operand rows goes out here"""
-    if tr.exchange == "referenced":
-        tr.rp.gather_referenced(x, tr.X_ref, stream)
-        return tr.plan_ref, tr.X_ref
-    tr.rp.gather_operand(x, tr.X_full, stream)
-    return tr.plan, tr.X_full
-
-
-class RowPartitionedLightGCNTrainer:
+class RowPartitionedLightGCNTrainer(_RowPartitioned):
     """LightGCN with the propagation ROW-PARTITIONED over the ranks: rank r owns the contiguous
     rows [lo, hi) of the joint adjacency, of E = [U; V], of the Adam slots and of every propagated layer.  One step at
     the reference's batch size:
@@ -455,35 +487,20 @@ class RowPartitionedLightGCNTrainer:
 
     def __init__(self, comm, U0: np.ndarray, V0: np.ndarray, adj, n_layers: int, lr: float, reg: float,
                  loss_eps: float = 1e-7, batch_rows: bool = True):
-        self.ows = _ordered_ws()      # parity mode (ordered_reductions()): workspace of the ordered gradient scatters; None = float atomics
-        from .dist import RowPartition
-        self.comm = comm
+        self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni
         self.ld = padded_ld(self.d, np.float32)
         self.L, self.lr, self.reg, self.loss_eps = n_layers, lr, reg, loss_eps
         self.batch_rows = bool(batch_rows)
         self._batch = {}
-        rp = self.rp = RowPartition(comm, self.n, self.ld)
-        lo, hi, pad = rp.lo, rp.hi, rp.rows_pad
-        indptr, indices, values = adj
-        blk_ptr = (indptr[lo:hi + 1] - indptr[lo]).astype(np.int64)
-        blk_ptr = np.concatenate([blk_ptr, np.full(pad - (hi - lo), blk_ptr[-1] if hi > lo else 0, np.int64)])   # pad rows: empty
-        sel = slice(int(indptr[lo]), int(indptr[hi]))
-        self.plan = SpmmPlan(blk_ptr, indices[sel], values[sel], self.ld)     # rows = this rank's block, columns global
-        _setup_row_exchange(self, adj, blk_ptr, sel)
-        E0 = np.zeros((self.n, self.ld), np.float32)
-        E0[:self.nu, :self.d] = U0; E0[self.nu:, :self.d] = V0
-        blk = np.zeros((pad, self.ld), np.float32); blk[:hi - lo] = E0[lo:hi]
-        self.E = DeviceBuffer.from_numpy(blk)
-        zb = lambda: DeviceBuffer.zeros((pad, self.ld), np.float32)
-        self.m, self.v, self.S, self.A, self.B = zb(), zb(), zb(), zb(), zb()
-        full = lambda: DeviceBuffer.zeros((rp.world * pad, self.ld), np.float32)
-        self.X_full, self.S_full, self.dE_full = full(), full(), full()
+        self.E = DeviceBuffer.from_numpy(self._init_rows(comm, adj, pack_joint(U0, V0, self.ld)))
+        self.opt = Adam(self.E, lr, n=(self.rp.hi - self.rp.lo) * self.ld)
+        zb = lambda: DeviceBuffer.zeros((self.rp.rows_pad, self.ld), np.float32)
+        self.S, self.A, self.B = zb(), zb(), zb()
+        self.S_full, self.dE_full = self._full(), self._full()
         self.d_loss = DeviceBuffer.zeros(1, np.float64)
-        f = np.float32
-        self.b1, self.b2, self.adam_eps = f(0.9), f(0.999), f(1e-8)
-        self.b1p, self.b2p = self.b1, self.b2
+        self.row_mask = None    # bitmap of the batch's rows over the whole table, allocated by the first batch-row step
 
     def _propagate(self, x, addend, accum, stream, whole_first=None, first_x_mask=None, last_y_mask=None):
         """L layers from the block ``x``: y = A_hat[lo:hi] gather(x) (+ addend), accumulated into ``accum`` if given.
@@ -494,7 +511,7 @@ class RowPartitionedLightGCNTrainer:
             if k == 0 and whole_first is not None:
                 plan, X = self.plan, whole_first
             else:
-                plan, X = _row_operand(self, x, stream)
+                plan, X = self._row_operand(x, stream)
             capi.spmm_csr(plan, X, y, self.ld, d_addend=addend, addend_scale=1.0 if addend is not None else 0.0,
                           d_accum=accum, stream=stream, d_x_row_mask=first_x_mask if (k == 0 and whole_first is not None) else None,
                           d_y_row_mask=last_y_mask if k == self.L - 1 else None)
@@ -518,7 +535,7 @@ class RowPartitionedLightGCNTrainer:
         rp, ld = self.rp, self.ld
         if not self.batch_rows or B == 0 or self.L == 0:
             return self._train_step_full(d_u, d_i, d_j, B, stream)
-        if getattr(self, "row_mask", None) is None:
+        if self.row_mask is None:
             self.row_mask = DeviceBuffer.zeros((rp.world * rp.rows_pad + 31) // 32, np.uint32)
         self.row_mask.fill_bytes(0, stream)
         capi.mark_batch_rows(d_u, d_i, d_j, B, self.nu, self.row_mask, stream)         # bitmap of {u, nu + i, nu + j} over the whole table
@@ -537,15 +554,7 @@ class RowPartitionedLightGCNTrainer:
         capi.batch_rows_scatter_add(self.dE_full, ld, 0, self.n, d_u, d_i, d_j, B, self.nu, b["dE"], stream)
         dE_blk = self.dE_full.ptr + rp.lo * ld * 4
         g = self._propagate(dE_blk, dE_blk, None, stream, whole_first=self.dE_full, first_x_mask=self.row_mask)
-        self._adam(g, stream)
-
-    def _adam(self, g, stream):
-        rp, ld = self.rp, self.ld
-        f = np.float32
-        alpha = float(f(f(self.lr) * np.sqrt(f(1) - self.b2p, dtype=f) / (f(1) - self.b1p)))
-        capi.adam_step(self.E, self.m, self.v, g, (rp.hi - rp.lo) * ld, 1.0 / (self.L + 1), alpha, float(self.b1), float(self.b2),
-                       float(self.adam_eps), stream)
-        self.b1p = f(self.b1p * self.b1); self.b2p = f(self.b2p * self.b2)
+        self.opt.step(g, 1.0 / (self.L + 1), stream)
 
     def _train_step_full(self, d_u, d_i, d_j, B: int, stream=None):
         """the step of rounds 2-3: every layer in full, the layer sum all-gathered, the batch gradient exchanged like any operand"""
@@ -558,7 +567,7 @@ class RowPartitionedLightGCNTrainer:
                                      self.reg, self.dE_full, self.d_loss, stream, ordered=self.ows)
         dE_blk = self.dE_full.ptr + rp.lo * ld * 4                       # this rank's rows of the batch gradient, in place
         g = self._propagate(dE_blk, dE_blk, None, stream)
-        self._adam(g, stream)
+        self.opt.step(g, 1.0 / (self.L + 1), stream)
 
     def loss(self, stream=None) -> float:
         return float(self.d_loss.numpy(stream)[0])
@@ -567,12 +576,7 @@ class RowPartitionedLightGCNTrainer:
         """(U, V) = split(mean(E0..EL)) (LightGCN.py:41), whole, on every rank"""
         self.forward_sum()
         self.rp.gather_operand(self.S, self.S_full)
-        Ebar = (self.S_full.numpy()[:self.n, :self.d] / np.float32(self.L + 1)).astype(np.float32)
-        return np.ascontiguousarray(Ebar[:self.nu]), np.ascontiguousarray(Ebar[self.nu:])
-
-    def block(self, buf) -> np.ndarray:
-        """this rank's rows of a block buffer (pad rows and pad columns dropped)"""
-        return buf.numpy()[:self.rp.hi - self.rp.lo, :self.d].copy()
+        return split_joint((self.S_full.numpy()[:self.n, :self.d] / np.float32(self.L + 1)).astype(np.float32), self.nu, self.d)
 
 
 class BprTfTrainer:
@@ -582,60 +586,34 @@ class BprTfTrainer:
     folded into the Adam kernel and its loss term comes from qrec_sumsq."""
 
     def __init__(self, U0, V0, lr: float, reg: float, loss_eps: float = 1e-6):
-        self.ows = _ordered_ws()      # parity mode (ordered_reductions()): workspace of the ordered gradient scatters; None = float atomics
+        self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni
         self.ld = padded_ld(self.d, np.float32)
         self.lr, self.reg, self.loss_eps = lr, reg, loss_eps
-        E0 = np.zeros((self.n, self.ld), np.float32)
-        E0[:self.nu, :self.d] = U0; E0[self.nu:, :self.d] = V0
-        self.E = DeviceBuffer.from_numpy(E0)
-        z = lambda: DeviceBuffer.zeros((self.n, self.ld), np.float32)
-        self.m, self.v, self.dE = z(), z(), z()
+        self.E = DeviceBuffer.from_numpy(pack_joint(U0, V0, self.ld))
+        self.opt = Adam(self.E, lr)
+        self.dE = DeviceBuffer.zeros((self.n, self.ld), np.float32)
         self.d_loss = DeviceBuffer.zeros(2, np.float64)      # [batch term, sum theta^2]
-        f = np.float32
-        self.b1, self.b2, self.adam_eps = f(0.9), f(0.999), f(1e-8)
-        self.b1p, self.b2p = self.b1, self.b2
 
     def train_step_async(self, d_u, d_i, d_j, B: int, stream=None):
-        f = np.float32
         self.dE.fill_bytes(0, stream); self.d_loss.fill_bytes(0, stream)
         capi.bpr_batch_loss_grad(self.E, 1.0, self.nu, self.n, self.ld, d_u, d_i, d_j, B, self.loss_eps, 0.0,
                                  self.dE, self.d_loss, stream, ordered=self.ows)
         capi.sumsq(self.E, capi.F32, self.n, self.d, self.ld, self.d_loss.ptr + 8, stream)   # loss is of the pre-update tables
-        alpha = float(f(f(self.lr) * np.sqrt(f(1) - self.b2p, dtype=f) / (f(1) - self.b1p)))
-        capi.adam_step(self.E, self.m, self.v, self.dE, self.n * self.ld, 1.0, alpha, float(self.b1), float(self.b2),
-                       float(self.adam_eps), stream, grad_l2=self.reg)
-        self.last_grad = (self.dE, 1.0, self.reg)
-        self.b1p = f(self.b1p * self.b1); self.b2p = f(self.b2p * self.b2)
+        self.opt.step(self.dE, stream=stream, grad_l2=self.reg)
 
     def loss(self, stream=None) -> float:
         batch, ss = self.d_loss.numpy(stream)
         return float(batch + self.reg * 0.5 * ss)
 
     def tables(self):
-        E = self.E.numpy()
-        return E[:self.nu, :self.d].copy(), E[self.nu:, :self.d].copy()
+        return split_joint(self.E.numpy(), self.nu, self.d)
 
     def gradients(self, before):
         """``before`` = [U; V] when the step started ([n, d]): the full-table L2 term of BPR.py:83 is reg * theta"""
-        g = _applied_gradient((self.last_grad[0], 1.0, 0.0))[:, :self.d] + np.float32(self.reg) * np.asarray(before, np.float32)
-        return g[:self.nu], g[self.nu:]
-
-
-def _applied_gradient(last, before=None):
-    """Host copy of what a step handed to Adam, BEFORE the update: ``last`` = (gradient buffer, scale, l2 coefficient) as the
-    trainers leave it after ``train_step_async`` (the buffers survive until the next step).  The reference's gradient is
-    scale * buffer + l2 * theta, theta the variable when the step started (``before``, padded like the buffer; needed only
-    when l2 != 0: the Adam kernel forms that term from theta itself).  Parity tests compare this with the gradients the
-    reference's ``minimize`` applied (tests/golden/tf_*.npz: grad<k>_<var>), before Adam's normalisation amplifies noise."""
-    buf, scale, l2 = last
-    g = buf.numpy().astype(np.float32) * np.float32(scale)
-    if l2:
-        if before is None:
-            raise ValueError("this gradient has a full-table L2 part: pass the variable's value at the start of the step")
-        g = g + np.float32(l2) * np.asarray(before, np.float32)
-    return g
+        pad = np.zeros((self.n, self.ld), np.float32); pad[:, :self.d] = before
+        return split_joint(self.opt.applied_gradient(pad), self.nu, self.d)
 
 
 def unique_first_appearance(idx: np.ndarray) -> np.ndarray:
@@ -653,18 +631,16 @@ class SimGCLTrainer:
 
     def __init__(self, U0, V0, adj, n_layers: int, lr: float, reg: float, cl_rate: float, eps: float,
                  tau: float = 0.2, loss_eps: float = 1e-7, seed: int = 0, max_unique: int = 4096):
-        self.ows = _ordered_ws()      # parity mode (ordered_reductions()): workspace of the ordered gradient scatters; None = float atomics
+        self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni
         self.ld = padded_ld(self.d, np.float32)
         self.L, self.lr, self.reg, self.cl_rate, self.eps, self.tau = n_layers, lr, reg, cl_rate, eps, tau
         self.loss_eps, self.seed = loss_eps, seed
         self.plan = SpmmPlan(adj[0], adj[1], adj[2], self.ld, split_row=self.nu)
-        E0 = np.zeros((self.n, self.ld), np.float32)
-        E0[:self.nu, :self.d] = U0; E0[self.nu:, :self.d] = V0
-        self.E = DeviceBuffer.from_numpy(E0)
+        self.E = DeviceBuffer.from_numpy(pack_joint(U0, V0, self.ld))
+        self.opt = Adam(self.E, lr)
         z = lambda: DeviceBuffer.zeros((self.n, self.ld), np.float32)
-        self.m, self.v = z(), z()
         self.Sm, self.S1, self.S2, self.dOut, self.A, self.B = z(), z(), z(), z(), z(), z()
         self.V = [[z(), z()], [z(), z()]]                      # ping-pong layer buffers of the two perturbed views
         self.d_loss = DeviceBuffer.zeros(2, np.float64)         # [rec, cl (unscaled)]
@@ -676,9 +652,6 @@ class SimGCLTrainer:
         self.ws_items = DeviceBuffer(capi.info_nce_workspace_bytes(max_unique, self.ld), np.uint8)
         self.side_stream, self.ev_fork, self.ev_join = capi.Stream(), capi.Event(), capi.Event()
         self.batch_rows = None  # capi.RowSubset of the step's rows
-        f = np.float32
-        self.b1, self.b2, self.adam_eps = f(0.9), f(0.999), f(1e-8)
-        self.b1p, self.b2p = self.b1, self.b2
         self.step_no = 0
         self.dp = None          # dist.BatchParallel
 
@@ -729,10 +702,6 @@ class SimGCLTrainer:
                 x[v] = yv
             x[0] = y0
 
-    def adam_alpha(self) -> float:
-        f = np.float32
-        return float(f(f(self.lr) * np.sqrt(f(1) - self.b2p, dtype=f) / (f(1) - self.b1p)))
-
     def train_step_async(self, d_u, d_i, d_j, B: int, d_uniq_users, n_uu: int, d_uniq_items, n_ui: int,
                          noises=None, stream=None, share=None):
         """u/i/j int32[B]; d_uniq_users: distinct user rows; d_uniq_items: distinct item rows
@@ -746,8 +715,7 @@ class SimGCLTrainer:
         lo, cnt = (0, B) if share is None else share
         cl_rate = self.cl_rate if self.dp is None else self.cl_rate / self.dp.world
         bound = min(3 * B, self.n)
-        if self.batch_rows is None or self.batch_rows.capacity < bound:
-            self.batch_rows = capi.RowSubset(bound)
+        self.batch_rows = _row_subset(self.batch_rows, bound)
         subset = capi.mark_compact_batch_rows(d_u, d_i, d_j, B, self.nu, self.n, self.row_mask, self.batch_rows, bound, stream,
                                               d_zero8=self.d_loss, n_zero8=2)          # ... and both loss accumulators cleared
         self._encode_three(noises, stream, self.row_mask, subset)
@@ -778,10 +746,7 @@ class SimGCLTrainer:
         if self.dp is not None:
             self.dp.all_reduce(g)
             self.dp.all_reduce(self.d_loss.head_view(1))      # rec term: shares add up; the cl term is whole on every rank
-        capi.adam_step(self.E, self.m, self.v, g, self.n * self.ld, 1.0 / L, self.adam_alpha(), float(self.b1),
-                       float(self.b2), float(self.adam_eps), stream)
-        self.last_grad = (g, 1.0 / L, 0.0)
-        self.b1p = np.float32(self.b1p * self.b1); self.b2p = np.float32(self.b2p * self.b2)
+        self.opt.step(g, 1.0 / L, stream)
         self.step_no += 1
 
     def losses(self, stream=None):
@@ -791,20 +756,17 @@ class SimGCLTrainer:
         return float(rec + cl), float(rec), float(cl)
 
     def gradients(self):
-        g = _applied_gradient(self.last_grad)[:, :self.d]
-        return g[:self.nu], g[self.nu:]
+        return split_joint(self.opt.applied_gradient(), self.nu, self.d)
 
     def main_embeddings(self):
         self._encode(self.Sm, 0)
-        m = (self.Sm.numpy()[:, :self.d] / np.float32(self.L)).astype(np.float32)
-        return np.ascontiguousarray(m[:self.nu]), np.ascontiguousarray(m[self.nu:])
+        return split_joint((self.Sm.numpy()[:, :self.d] / np.float32(self.L)).astype(np.float32), self.nu, self.d)
 
     def ego_embeddings(self):
-        E = self.E.numpy()
-        return E[:self.nu, :self.d].copy(), E[self.nu:, :self.d].copy()
+        return split_joint(self.E.numpy(), self.nu, self.d)
 
 
-class RowPartitionedSimGCLTrainer:
+class RowPartitionedSimGCLTrainer(_RowPartitioned):
     """SimGCL with every node table ROW-PARTITIONED over the ranks (BASELINE config #5).  Rank r owns rows
     [lo, hi) of E and its Adam slots, of the adjacency, and of the three encoders' layer outputs and layer sums.  One step
     at the reference's batch size, the same step as ``SimGCLTrainer``:
@@ -822,44 +784,27 @@ class RowPartitionedSimGCLTrainer:
 
     def __init__(self, comm, U0, V0, adj, n_layers: int, lr: float, reg: float, cl_rate: float, eps: float,
                  tau: float = 0.2, loss_eps: float = 1e-7, seed: int = 0, max_unique: int = 4096, batch_rows: bool = True):
-        self.ows = _ordered_ws()      # parity mode (ordered_reductions()): workspace of the ordered gradient scatters; None = float atomics
-        from .dist import RowPartition
-        self.comm = comm
+        self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni
         self.ld = padded_ld(self.d, np.float32)
         self.L, self.lr, self.reg, self.cl_rate, self.eps, self.tau = n_layers, lr, reg, cl_rate, eps, tau
         self.loss_eps, self.seed = loss_eps, seed
-        rp = self.rp = RowPartition(comm, self.n, self.ld)
-        lo, hi, pad = rp.lo, rp.hi, rp.rows_pad
-        indptr, indices, values = adj
-        blk_ptr = (indptr[lo:hi + 1] - indptr[lo]).astype(np.int64)
-        blk_ptr = np.concatenate([blk_ptr, np.full(pad - (hi - lo), blk_ptr[-1] if hi > lo else 0, np.int64)])   # pad rows: empty
-        sel = slice(int(indptr[lo]), int(indptr[hi]))
-        self.plan = SpmmPlan(blk_ptr, indices[sel], values[sel], self.ld)     # rows = this rank's block, columns global
-        _setup_row_exchange(self, adj, blk_ptr, sel)
-        E0 = np.zeros((self.n, self.ld), np.float32)
-        E0[:self.nu, :self.d] = U0; E0[self.nu:, :self.d] = V0
-        blk = np.zeros((pad, self.ld), np.float32); blk[:hi - lo] = E0[lo:hi]
-        self.E = DeviceBuffer.from_numpy(blk)
-        zb = lambda: DeviceBuffer.zeros((pad, self.ld), np.float32)
-        self.m, self.v = zb(), zb()
+        self.E = DeviceBuffer.from_numpy(self._init_rows(comm, adj, pack_joint(U0, V0, self.ld)))
+        self.opt = Adam(self.E, lr, n=(self.rp.hi - self.rp.lo) * self.ld)
+        zb = lambda: DeviceBuffer.zeros((self.rp.rows_pad, self.ld), np.float32)
         self.Sm, self.S1, self.S2, self.A, self.B = zb(), zb(), zb(), zb(), zb()
         self.V = [[zb(), zb()], [zb(), zb()]]
-        full = lambda: DeviceBuffer.zeros((rp.world * pad, self.ld), np.float32)
-        self.X_full, self.Sm_full, self.S1_full, self.S2_full, self.dOut_full = full(), full(), full(), full(), full()
+        self.Sm_full, self.S1_full, self.S2_full, self.dOut_full = self._full(), self._full(), self._full(), self._full()
         self.d_loss = DeviceBuffer.zeros(2, np.float64)         # [rec, cl (unscaled)]
-        self.batch_rows, self._cmp = bool(batch_rows), None
+        self.batch_rows, self._cmp = bool(batch_rows), None     # _cmp: the packed batch-row tables of the last batch size
         self.max_unique = max_unique
         self.ws = DeviceBuffer(capi.info_nce_workspace_bytes(max_unique, self.ld), np.uint8)
-        f = np.float32
-        self.b1, self.b2, self.adam_eps = f(0.9), f(0.999), f(1e-8)
-        self.b1p, self.b2p = self.b1, self.b2
         self.step_no = 0
 
     def _product(self, x, y, stream, accum=None, addend=None):
         """y = the rank's rows of A_hat gather(x) (+ addend); accum += y"""
-        plan, X = _row_operand(self, x, stream)
+        plan, X = self._row_operand(x, stream)
         capi.spmm_csr(plan, X, y, self.ld, d_addend=addend, addend_scale=1.0 if addend is not None else 0.0,
                       d_accum=accum, stream=stream)
 
@@ -895,7 +840,7 @@ class RowPartitionedSimGCLTrainer:
         rp, ld, L = self.rp, self.ld, float(self.L)
         self._encode_three(noises, stream)
         cl = self.d_loss.ptr + 8
-        whole_first = getattr(self, "batch_rows", True) and B > 0
+        whole_first = self.batch_rows and B > 0
         if whole_first:
             # round 4 -- the losses read the three layer sums at the batch's rows only: Sm at {u, nu + i, nu + j} (3B rows), S1 / S2 at the batch's
             # unique users and items.  Every rank contributes its rows of those (zeros elsewhere) into ONE packed buffer
@@ -903,7 +848,7 @@ class RowPartitionedSimGCLTrainer:
             # all-gathers of N x ld = 53 MB), the losses run on it with the rows addressed by position, and every rank -- holding the whole
             # batch gradient -- scatters it into a whole-height operand that the first backward product reads without any exchange
             M = self.max_unique
-            if getattr(self, "_cmp", None) is None or self._cmp["B"] != B:
+            if self._cmp is None or self._cmp["B"] != B:
                 ar = np.arange(max(3 * B, 2 * M), dtype=np.int32)
                 self._cmp = dict(B=B, S=DeviceBuffer.zeros((3 * B + 4 * M, ld), np.float32), dSm=DeviceBuffer.zeros((3 * B, ld), np.float32),
                                  dC=DeviceBuffer.zeros((2 * M, ld), np.float32), ar=DeviceBuffer.from_numpy(ar), arB=DeviceBuffer.from_numpy(ar[:B] + B))
@@ -949,10 +894,7 @@ class RowPartitionedSimGCLTrainer:
             x = y
         g = self.B if x is self.A else self.A
         product(x, g, None, self.L == 1)
-        f = np.float32
-        alpha = float(f(f(self.lr) * np.sqrt(f(1) - self.b2p, dtype=f) / (f(1) - self.b1p)))
-        capi.adam_step(self.E, self.m, self.v, g, (rp.hi - rp.lo) * ld, 1.0 / L, alpha, float(self.b1), float(self.b2), float(self.adam_eps), stream)
-        self.b1p = f(self.b1p * self.b1); self.b2p = f(self.b2p * self.b2)
+        self.opt.step(g, 1.0 / L, stream)
         self.step_no += 1
 
     def losses(self, stream=None):
@@ -969,34 +911,7 @@ class RowPartitionedSimGCLTrainer:
             self._product(x, y, None, accum=self.Sm)
             x = y
         self.rp.gather_operand(self.Sm, self.Sm_full)
-        m = (self.Sm_full.numpy()[:self.n, :self.d] / np.float32(self.L)).astype(np.float32)
-        return np.ascontiguousarray(m[:self.nu]), np.ascontiguousarray(m[self.nu:])
-
-    def block(self, buf) -> np.ndarray:
-        return buf.numpy()[:self.rp.hi - self.rp.lo, :self.d].copy()
-
-
-class _Adam:
-    """host-side bookkeeping of one TF-1.14 Adam slot set (fp32 beta powers)"""
-
-    def __init__(self, theta: DeviceBuffer, lr: float):
-        self.theta = theta
-        self.m = DeviceBuffer.zeros(theta.shape, np.float32); self.v = DeviceBuffer.zeros(theta.shape, np.float32)
-        f = np.float32
-        self.lr, self.b1, self.b2, self.eps = f(lr), f(0.9), f(0.999), f(1e-8)
-        self.b1p, self.b2p = self.b1, self.b2
-        self.n = int(np.prod(theta.shape))
-
-    def step(self, grad, grad_scale=1.0, stream=None, grad_l2=0.0):
-        f = np.float32
-        alpha = float(f(self.lr * np.sqrt(f(1) - self.b2p, dtype=f) / (f(1) - self.b1p)))
-        capi.adam_step(self.theta, self.m, self.v, grad, self.n, grad_scale, alpha, float(self.b1), float(self.b2),
-                       float(self.eps), stream, grad_l2=grad_l2)
-        self.b1p = f(self.b1p * self.b1); self.b2p = f(self.b2p * self.b2)
-        self.last = (grad, grad_scale, grad_l2)
-
-    def applied_gradient(self, before=None):
-        return _applied_gradient(self.last, before)
+        return split_joint((self.Sm_full.numpy()[:self.n, :self.d] / np.float32(self.L)).astype(np.float32), self.nu, self.d)
 
 
 class NGCFTrainer:
@@ -1008,7 +923,7 @@ class NGCFTrainer:
     N_LAYERS = 2
 
     def __init__(self, U0, V0, W, adj, lr: float, reg: float, loss_eps: float = 1e-7, seed: int = 0):
-        self.ows = _ordered_ws()      # parity mode (ordered_reductions()): workspace of the ordered gradient scatters; None = float atomics
+        self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni
         if 3 * self.d > 256:
@@ -1017,10 +932,8 @@ class NGCFTrainer:
         self.wide_d, self.wide_ld = 3 * self.d, padded_ld(3 * self.d, np.float32)
         self.lr, self.reg, self.loss_eps, self.seed = lr, reg, loss_eps, seed
         self.plan = SpmmPlan(adj[0], adj[1], adj[2], self.ld, split_row=self.nu)
-        E0 = np.zeros((self.n, self.ld), np.float32)
-        E0[:self.nu, :self.d] = U0; E0[self.nu:, :self.d] = V0
         z = lambda: DeviceBuffer.zeros((self.n, self.ld), np.float32)
-        self.E = [DeviceBuffer.from_numpy(E0), z(), z()]          # E_0 (parameters), E_1, E_2
+        self.E = [DeviceBuffer.from_numpy(pack_joint(U0, V0, self.ld)), z(), z()]          # E_0 (parameters), E_1, E_2
         self.side = [z(), z()]; self.gate = [z(), z()]
         self.inv = [DeviceBuffer.zeros(self.n, np.float32), DeviceBuffer.zeros(self.n, np.float32)]
         self.dpre, self.dside, self.dEa, self.dEb = z(), z(), z(), z()
@@ -1034,8 +947,8 @@ class NGCFTrainer:
         self.W = [[capi.DeviceSlice(self.W_all, (2 * k + t) * ll, (self.ld, self.ld)) for t in range(2)] for k in range(2)]
         self.gW = [[capi.DeviceSlice(self.gW_all, (2 * k + t) * ll, (self.ld, self.ld)) for t in range(2)] for k in range(2)]
         self.partial = DeviceBuffer(capi.ngcf_wgrad_partial_bytes(self.n, self.ld), np.uint8)
-        self.optE = _Adam(self.E[0], lr)
-        self.optW = _Adam(self.W_all, lr)
+        self.optE = Adam(self.E[0], lr)
+        self.optW = Adam(self.W_all, lr)
         self.d_loss = DeviceBuffer.zeros(1, np.float64)
         self.row_mask = DeviceBuffer.zeros((self.n + 31) // 32, np.uint32)
         self.batch_rows = None  # capi.RowSubset of the step's rows (ld <= 64: the last layer runs on these rows only)
@@ -1065,8 +978,7 @@ class NGCFTrainer:
         subset = None
         if B and ld <= 64:
             bound = min(3 * B, n)
-            if self.batch_rows is None or self.batch_rows.capacity < bound:
-                self.batch_rows = capi.RowSubset(bound)
+            self.batch_rows = _row_subset(self.batch_rows, bound)
             subset = capi.mark_compact_batch_rows(d_u, d_i, d_j, B, self.nu, n, self.row_mask, self.batch_rows, bound, stream,
                                                   d_zero8=self.d_loss, n_zero8=1)
         else:
@@ -1111,21 +1023,19 @@ class NGCFTrainer:
     def inference_embeddings(self):
         """3d-wide (U, V) of the inference graph (isTraining = 0, NGCF.py:65-69)."""
         self.forward(False)
-        A = self.All.numpy()[:, :self.wide_d]
-        return np.ascontiguousarray(A[:self.nu]), np.ascontiguousarray(A[self.nu:])
+        return split_joint(self.All.numpy(), self.nu, self.wide_d)
 
     def parameters(self):
-        E = self.E[0].numpy()[:, :self.d]
-        return E[:self.nu].copy(), E[self.nu:].copy(), [[w.numpy()[:self.d, :self.d].copy() for w in pair] for pair in self.W]
+        return (*split_joint(self.E[0].numpy(), self.nu, self.d), [[w.numpy()[:self.d, :self.d].copy() for w in pair] for pair in self.W])
 
     def gradients(self):
         """(dU, dV, [[dW1, dW2] per layer]) of the last step, before Adam"""
-        g = self.optE.applied_gradient()[:, :self.d]
         gw = self.optW.applied_gradient()
-        return g[:self.nu], g[self.nu:], [[gw[2 * k + t, :self.d, :self.d] for t in range(2)] for k in range(2)]
+        return (*split_joint(self.optE.applied_gradient(), self.nu, self.d),
+                [[gw[2 * k + t, :self.d, :self.d] for t in range(2)] for k in range(2)])
 
 
-class RowPartitionedNGCFTrainer:
+class RowPartitionedNGCFTrainer(_RowPartitioned):
     """NGCF with every node table ROW-PARTITIONED over the ranks (BASELINE config #5: "row-shard the tables,
     all-reduce for the dense layers").  Rank r owns rows [lo, hi) of E_0 and its Adam slots, of the adjacency, and of every
     per-layer table (side, gate, E_k, 1/|.|); the four d x d weights and their Adam slots are replicated.  One step at
@@ -1148,9 +1058,7 @@ class RowPartitionedNGCFTrainer:
     N_LAYERS = 2
 
     def __init__(self, comm, U0, V0, W, adj, lr: float, reg: float, loss_eps: float = 1e-7, seed: int = 0, batch_rows: bool = True):
-        self.ows = _ordered_ws()      # parity mode (ordered_reductions()): workspace of the ordered gradient scatters; None = float atomics
-        from .dist import RowPartition
-        self.comm = comm
+        self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni
         if 3 * self.d > 256:
@@ -1159,26 +1067,14 @@ class RowPartitionedNGCFTrainer:
         self.wide_d, self.wide_ld = 3 * self.d, padded_ld(3 * self.d, np.float32)
         self.lr, self.reg, self.loss_eps, self.seed = lr, reg, loss_eps, seed
         self.batch_rows, self._batch = bool(batch_rows), {}
-        rp = self.rp = RowPartition(comm, self.n, self.ld)
-        lo, hi, pad = rp.lo, rp.hi, rp.rows_pad
-        indptr, indices, values = adj
-        blk_ptr = (indptr[lo:hi + 1] - indptr[lo]).astype(np.int64)
-        blk_ptr = np.concatenate([blk_ptr, np.full(pad - (hi - lo), blk_ptr[-1] if hi > lo else 0, np.int64)])   # pad rows: empty
-        sel = slice(int(indptr[lo]), int(indptr[hi]))
-        self.plan = SpmmPlan(blk_ptr, indices[sel], values[sel], self.ld)     # rows = this rank's block, columns global
-        _setup_row_exchange(self, adj, blk_ptr, sel)
-        E0 = np.zeros((self.n, self.ld), np.float32)
-        E0[:self.nu, :self.d] = U0; E0[self.nu:, :self.d] = V0
-        blk = np.zeros((pad, self.ld), np.float32); blk[:hi - lo] = E0[lo:hi]
+        blk = self._init_rows(comm, adj, pack_joint(U0, V0, self.ld))
+        pad = self.rp.rows_pad
         zb = lambda: DeviceBuffer.zeros((pad, self.ld), np.float32)
         self.E = [DeviceBuffer.from_numpy(blk), zb(), zb()]
         self.side = [zb(), zb()]; self.gate = [zb(), zb()]; self.z = [zb(), zb()]
         self.inv = [DeviceBuffer.zeros(pad, np.float32), DeviceBuffer.zeros(pad, np.float32)]
         self.dpre, self.dside, self.dEa, self.dEb = zb(), zb(), zb(), zb()
-        rows_full = rp.world * pad
-        self.X_full = DeviceBuffer.zeros((rows_full, self.ld), np.float32)
-        self.All_full = DeviceBuffer.zeros((rows_full, self.wide_ld), np.float32)
-        self.dAll_full = DeviceBuffer.zeros((rows_full, self.wide_ld), np.float32)
+        self.All_full, self.dAll_full = self._full(self.wide_ld), self._full(self.wide_ld)
         ll = self.ld * self.ld
         padw = lambda w: np.pad(np.asarray(w, np.float32), ((0, self.ld - self.d), (0, self.ld - self.d)))
         self.W_all = DeviceBuffer.from_numpy(np.stack([padw(w) for pair in W for w in pair]))
@@ -1186,7 +1082,7 @@ class RowPartitionedNGCFTrainer:
         self.W = [[capi.DeviceSlice(self.W_all, (2 * k + t) * ll, (self.ld, self.ld)) for t in range(2)] for k in range(2)]
         self.gW = [[capi.DeviceSlice(self.gW_all, (2 * k + t) * ll, (self.ld, self.ld)) for t in range(2)] for k in range(2)]
         self.partial = DeviceBuffer(capi.ngcf_wgrad_partial_bytes(pad, self.ld), np.uint8)
-        self.optE, self.optW = _Adam(self.E[0], lr), _Adam(self.W_all, lr)
+        self.optE, self.optW = Adam(self.E[0], lr), Adam(self.W_all, lr)
         self.d_loss = DeviceBuffer.zeros(1, np.float64)
         self.step_no = 0
 
@@ -1204,7 +1100,7 @@ class RowPartitionedNGCFTrainer:
                 capi.copy_cols(self.All_full, self.wide_ld, self.X_full, ld, 0, rows_full, d, False, stream)
                 plan, X = self.plan, self.X_full
             else:
-                plan, X = _row_operand(self, self.E[k], stream)
+                plan, X = self._row_operand(self.E[k], stream)
             capi.spmm_csr(plan, X, self.side[k], ld, stream=stream)
             capi.ngcf_dense_fwd(self.E[k], self.side[k], self.W[k][0], self.W[k][1], pad, ld, self.gate[k], stream)
             capi.ngcf_activate(self.gate[k], pad, d, ld, self.KEEP if training else 1.0, None if masks is None else masks[k],
@@ -1252,7 +1148,7 @@ class RowPartitionedNGCFTrainer:
             capi.ngcf_layer_bwd(dnext, self.dAll_full.ptr + mine, self.All_full.ptr + mine, self.wide_ld, (k + 1) * d, self.inv[k],
                                 self.gate[k], self.E[k], self.side[k], self.W[k][0], self.W[k][1], pad, d, ld, self.dpre, self.dside, dE,
                                 self.partial, self.gW[k][0], self.gW[k][1], stream)
-            plan, X = _row_operand(self, self.dside, stream)             # dE += (A_hat dside)[lo:hi]
+            plan, X = self._row_operand(self.dside, stream)            # dE += (A_hat dside)[lo:hi]
             capi.spmm_csr(plan, X, dE, ld, d_addend=dE, addend_scale=1.0, stream=stream)
             dnext = dE
         capi.copy_cols(dnext, ld, self.dAll_full.ptr + mine, self.wide_ld, 0, pad, d, True, stream)   # + ego block of the concat
@@ -1267,12 +1163,7 @@ class RowPartitionedNGCFTrainer:
     def inference_embeddings(self):
         """3d-wide (U, V) of the inference graph (isTraining = 0, NGCF.py:65-69), whole, on every rank"""
         self.forward(False)
-        A = self.All_full.numpy()[:self.n, :self.wide_d]
-        return np.ascontiguousarray(A[:self.nu]), np.ascontiguousarray(A[self.nu:])
-
-    def block(self, buf) -> np.ndarray:
-        """this rank's rows of a block buffer (pad rows and pad columns dropped)"""
-        return buf.numpy()[:self.rp.hi - self.rp.lo, :self.d].copy()
+        return split_joint(self.All_full.numpy()[:self.n], self.nu, self.wide_d)
 
     def weights(self):
         return [[w.numpy()[:self.d, :self.d].copy() for w in pair] for pair in self.W]
@@ -1287,25 +1178,24 @@ class SGLTrainer:
 
     def __init__(self, U0, V0, adj, n_layers: int, lr: float, reg: float, ssl_reg: float, temp: float,
                  loss_eps: float = 1e-7, max_unique: int = 8192):
-        self.ows = _ordered_ws()      # parity mode (ordered_reductions()): workspace of the ordered gradient scatters; None = float atomics
+        self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni
         self.ld = padded_ld(self.d, np.float32)
         self.L, self.reg, self.ssl_reg, self.temp, self.loss_eps = n_layers, reg, ssl_reg, temp, loss_eps
         self.main_plan = SpmmPlan(adj[0], adj[1], adj[2], self.ld, split_row=self.nu)
         self.plans = [None, None]                 # per view: list of L plans
-        E0 = np.zeros((self.n, self.ld), np.float32)
-        E0[:self.nu, :self.d] = U0; E0[self.nu:, :self.d] = V0
-        self.E = DeviceBuffer.from_numpy(E0)
+        self.E = DeviceBuffer.from_numpy(pack_joint(U0, V0, self.ld))
         z = lambda: DeviceBuffer.zeros((self.n, self.ld), np.float32)
         self.S = [z(), z(), z()]                  # layer sums of main, view 1, view 2
         self.dOut = [z(), z(), z()]
         self.G, self.A, self.B = z(), z(), z()
-        self.opt = _Adam(self.E, lr)
+        self.opt = Adam(self.E, lr)
         self.d_loss = DeviceBuffer.zeros(2, np.float64)     # [rec, ssl (unscaled)]
         self.row_mask = DeviceBuffer.zeros((self.n + 31) // 32, np.uint32)
         self.max_unique = max_unique
         self.ws = DeviceBuffer(capi.info_nce_workspace_bytes(max_unique, self.ld), np.uint8)
+        self.batch_rows = None  # capi.RowSubset of the step's rows
 
     def set_subgraphs(self, adjs1, adjs2):
         """adjs*: one (indptr, indices, values) triple, or a list of L of them (random walk)."""
@@ -1368,8 +1258,7 @@ class SGLTrainer:
         # the batch's rows as bitmap + list (one launch, loss accumulators cleared with it): the three output gradients are written
         # and read at those rows only (operand / addend masks of the backward products), so only those rows are cleared
         bound = min(3 * B, self.n)
-        if getattr(self, "batch_rows", None) is None or self.batch_rows.capacity < bound:
-            self.batch_rows = capi.RowSubset(bound)
+        self.batch_rows = _row_subset(self.batch_rows, bound)
         subset = capi.mark_compact_batch_rows(d_u, d_i, d_j, B, self.nu, self.n, self.row_mask, self.batch_rows, bound, stream,
                                               d_zero8=self.d_loss, n_zero8=2)
         for v in range(3):
@@ -1395,17 +1284,14 @@ class SGLTrainer:
         return float(rec + self.ssl_reg * ssl), float(rec), float(self.ssl_reg * ssl)
 
     def gradients(self):
-        g = self.opt.applied_gradient()[:, :self.d]
-        return g[:self.nu], g[self.nu:]
+        return split_joint(self.opt.applied_gradient(), self.nu, self.d)
 
     def main_embeddings(self):
         self._forward(0)
-        m = (self.S[0].numpy()[:, :self.d] / np.float32(self.L + 1)).astype(np.float32)
-        return np.ascontiguousarray(m[:self.nu]), np.ascontiguousarray(m[self.nu:])
+        return split_joint((self.S[0].numpy()[:, :self.d] / np.float32(self.L + 1)).astype(np.float32), self.nu, self.d)
 
     def ego_embeddings(self):
-        E = self.E.numpy()
-        return E[:self.nu, :self.d].copy(), E[self.nu:, :self.d].copy()
+        return split_joint(self.E.numpy(), self.nu, self.d)
 
 
 class BUIRTrainer:
@@ -1417,7 +1303,7 @@ class BUIRTrainer:
     computed at the batch's rows only."""
 
     def __init__(self, U0, V0, W0, b0, n_layers: int, lr: float, tau: float):
-        self.ows = _ordered_ws()      # parity mode (ordered_reductions()): workspace of the ordered gradient scatters; None = float atomics
+        self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni
         self.ld = padded_ld(self.d, np.float32)
@@ -1426,9 +1312,8 @@ class BUIRTrainer:
         if n_layers < 1:
             raise ValueError("BUIR needs at least one propagation layer")
         self.L, self.tau = n_layers, float(np.float32(tau))
-        E0 = np.zeros((self.n, self.ld), np.float32)
-        E0[:self.nu, :self.d] = U0; E0[self.nu:, :self.d] = V0
-        self.E, self.T = DeviceBuffer.from_numpy(E0), DeviceBuffer.from_numpy(E0)      # target starts as a copy (BUIR.py:85-86)
+        E0 = pack_joint(U0, V0, self.ld)
+        self.E, self.T = DeviceBuffer.from_numpy(E0), DeviceBuffer.from_numpy(E0)     # target starts as a copy (BUIR.py:85-86)
         Wp = np.zeros((self.ld, self.ld), np.float32); Wp[:self.d, :self.d] = W0
         bp = np.zeros(self.ld, np.float32); bp[:self.d] = np.asarray(b0, np.float32).reshape(-1)
         self.W, self.b = DeviceBuffer.from_numpy(Wp), DeviceBuffer.from_numpy(bp)
@@ -1436,7 +1321,7 @@ class BUIRTrainer:
         self.S_on, self.S_tar, self.dS, self.A, self.B = z(), z(), z(), z(), z()
         self.gW, self.gb = DeviceBuffer.zeros((self.ld, self.ld), np.float32), DeviceBuffer.zeros(self.ld, np.float32)
         self.wscratch = DeviceBuffer(capi.buir_wgrad_scratch_bytes(self.ld), np.uint8)
-        self.optE, self.optW, self.optb = _Adam(self.E, lr), _Adam(self.W, lr), _Adam(self.b, lr)
+        self.optE, self.optW, self.optb = Adam(self.E, lr), Adam(self.W, lr), Adam(self.b, lr)
         self.row_mask = DeviceBuffer.zeros((self.n + 31) // 32, np.uint32)
         self.d_loss = DeviceBuffer.zeros(1, np.float64)
         self.plan_o = self.plan_t = None
@@ -1657,20 +1542,18 @@ class SEPTTrainer:
 
     def __init__(self, U0, V0, adj, friend, sharing, n_layers: int, lr: float, reg: float, ss_rate: float, ins_cnt: int,
                  loss_eps: float = 1e-7, max_unique: int = 4096):
-        self.ows = _ordered_ws()      # parity mode (ordered_reductions()): workspace of the ordered gradient scatters; None = float atomics
+        self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni
         self.ld = padded_ld(self.d, np.float32)
         self.L, self.lr, self.reg, self.ss_rate, self.k, self.loss_eps = n_layers, lr, reg, ss_rate, ins_cnt, loss_eps
-        W0 = np.zeros((self.n, self.ld), np.float32)
-        W0[:self.nu, :self.d] = U0; W0[self.nu:, :self.d] = V0
-        self.W = DeviceBuffer.from_numpy(W0)
+        self.W = DeviceBuffer.from_numpy(pack_joint(U0, V0, self.ld))
         z = lambda: DeviceBuffer.zeros((self.n, self.ld), np.float32)
         self.E0, self.dE0, self.T, self.G = z(), z(), z(), [z(), z()]
         self.pref, self.aug = _View(self.n, self.ld, n_layers), _View(self.n, self.ld, n_layers)
         self.friend, self.sharing = _View(self.nu, self.ld, n_layers), _View(self.nu, self.ld, n_layers)
         self.pref.set_matrix(adj, split_row=self.nu); self.friend.set_matrix(friend); self.sharing.set_matrix(sharing)
-        self.opt = [_Adam(self.W, lr), _Adam(self.W, lr)]          # v1_opt (rec_loss), v2_opt (rec + ss), SEPT.py:267-270
+        self.opt = [Adam(self.W, lr), Adam(self.W, lr)]          # v1_opt (rec_loss), v2_opt (rec + ss), SEPT.py:267-270
         self.d_loss = DeviceBuffer.zeros(3, np.float64)             # [bpr term, sum W^2, neighbour-discrimination (unscaled)]
         self.row_mask = DeviceBuffer.zeros((self.n + 31) // 32, np.uint32)   # the batch's rows {u, nu+i, nu+j}
         self.max_unique = max_unique
@@ -1725,8 +1608,7 @@ class SEPTTrainer:
     def gradients(self, before):
         """(dU, dV) of the last step, before Adam; ``before`` = [U; V] when the step started ([n, d])"""
         pad = np.zeros((self.n, self.ld), np.float32); pad[:, :self.d] = before
-        g = self.last_opt.applied_gradient(pad)[:, :self.d]
-        return g[:self.nu], g[self.nu:]
+        return split_joint(self.last_opt.applied_gradient(pad), self.nu, self.d)
 
     def losses(self, stream=None):
         """(rec_loss, ss_rate * neighbor_dis_loss) as the reference prints them (SEPT.py:292, 301)"""
@@ -1737,12 +1619,10 @@ class SEPTTrainer:
         """(rec_user_embeddings, rec_item_embeddings) (SEPT.py:207-208): layer SUM of the preference view"""
         self._halve()
         self.pref.forward(self.E0)
-        S = self.pref.S.numpy()[:, :self.d]
-        return np.ascontiguousarray(S[:self.nu]), np.ascontiguousarray(S[self.nu:])
+        return split_joint(self.pref.S.numpy(), self.nu, self.d)
 
     def variables(self):
-        W = self.W.numpy()[:, :self.d]
-        return W[:self.nu].copy(), W[self.nu:].copy()
+        return split_joint(self.W.numpy(), self.nu, self.d)
 
 
 # ======================================================================================================================
@@ -1802,7 +1682,7 @@ class MHCNTrainer:
 
     def __init__(self, U0, V0, weights, H, R, n_layers: int, lr: float, reg: float, ss_rate: float, loss_eps: float = 1e-7,
                  seed: int = 0):
-        self.ows = _ordered_ws()      # parity mode (ordered_reductions()): workspace of the ordered gradient scatters; None = float atomics
+        self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni
         ld = self.ld = padded_ld(self.d, np.float32)
@@ -1818,8 +1698,8 @@ class MHCNTrainer:
             arr = pad1(val) if np.asarray(val).shape[0] == 1 else pad2(val)
             self.w[key] = DeviceBuffer.from_numpy(arr)
             self.g[key] = DeviceBuffer.zeros(arr.shape, np.float32)
-            self.opt[key] = _Adam(self.w[key], lr)
-        self.optU, self.optV = _Adam(self.U, lr), _Adam(self.V, lr)
+            self.opt[key] = Adam(self.w[key], lr)
+        self.optU, self.optV = Adam(self.U, lr), Adam(self.V, lr)
         self.planH = [SpmmPlan(*_csr_triple(h), ld) for h in H]
         self.planHT = [SpmmPlan(*_csr_triple(h.T), ld) for h in H]
         self.planR, self.planRT = SpmmPlan(*_csr_triple(R), ld), SpmmPlan(*_csr_triple(R.T), ld)
@@ -1998,8 +1878,7 @@ class MHCNTrainer:
     def final_embeddings(self):
         """(final_user_embeddings, final_item_embeddings) (MHCN.py:172-174, 226)"""
         self.forward()
-        F = self.F.numpy()[:, :self.d]
-        return np.ascontiguousarray(F[:self.nu]), np.ascontiguousarray(F[self.nu:])
+        return split_joint(self.F.numpy(), self.nu, self.d)
 
     def parameters(self):
         d = self.d

@@ -487,8 +487,8 @@ def test_simgcl_training_steps_match_restatement(L):
             u = d["train_u"][sel].astype(np.int32); i = d["train_i"][sel].astype(np.int32); j = rng.integers(0, ni, B).astype(np.int32)
             noises = [rng.random((N, dim)).astype(np.float32) for _ in range(2 * L)]
             if forced:
-                tr.E.upload(pad_cols(ref.E, tr.ld)); tr.m.upload(pad_cols(ref.opt.m, tr.ld)); tr.v.upload(pad_cols(ref.opt.v, tr.ld))
-                assert tr.b1p == ref.opt.b1p and tr.b2p == ref.opt.b2p
+                tr.E.upload(pad_cols(ref.E, tr.ld)); tr.opt.m.upload(pad_cols(ref.opt.m, tr.ld)); tr.opt.v.upload(pad_cols(ref.opt.v, tr.ld))
+                assert tr.opt.b1p == ref.opt.b1p and tr.opt.b2p == ref.opt.b2p
                 _, _, _, g_ref = ref.loss_and_grad(u, i, j, noises)
             lref, rec_ref, cl_ref = ref.train_step(u, i, j, noises)
             uu = unique_first_appearance(u); vv = (unique_first_appearance(i) + nu).astype(np.int32)

@@ -44,7 +44,7 @@ for rep in range(20):
 spmm_ms = float(np.median(ts)); nnz = tr.plan.nnz; N = nu + ni
 ts = []
 for rep in range(20):
-    e0.record(); capi.adam_step(tr.E, tr.m, tr.v, tr.A, N * tr.ld, 0.25, 1e-9); e1.record(); e1.sync(); ts.append(e1.elapsed_ms_since(e0))
+    e0.record(); capi.adam_step(tr.E, tr.opt.m, tr.opt.v, tr.A, N * tr.ld, 0.25, 1e-9); e1.record(); e1.sync(); ts.append(e1.elapsed_ms_since(e0))
 adam_ms = float(np.median(ts))
 alg = tr.plan.bytes_algorithmic(a.dim) + N * a.dim * 4   # + accum RMW read
 out = dict(workload=f"LightGCN L={a.layers} d={a.dim} batch={B} {a.shape}-shape N={N} nnz={nnz}", spmm_chunks=tr.plan.chunks, ms_per_step=dt * 1e3, host_enqueue_ms_per_step=t_host * 1e3, ms_per_step_with_loss_readback=dt_sync * 1e3,

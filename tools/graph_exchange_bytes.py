@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Bytes a rank receives per propagation product under the two operand exchanges of the row-partitioned graph trainers
-(qrec_amd/graph.py::_setup_row_exchange): all-gather of every block vs only the remote rows the rank's block of the adjacency
+(qrec_amd/graph.py::_RowPartitioned): all-gather of every block vs only the remote rows the rank's block of the adjacency
 refers to (dist.RowPartition.reference).  Host arithmetic on the two synthetic Yelp2018-shape graphs, world 8, d = 64 -- no
 GPU needed; prints one JSON object (committed as profiles/r03_graph_exchange_bytes.json; round 4 adds the batch-row economies: profiles/r04_graph_exchange_bytes.json)."""
 import json, os, sys
