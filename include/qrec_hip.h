@@ -489,6 +489,24 @@ int qrec_subgraph_values(const int32_t *d_u, const int32_t *d_i, const int32_t *
                          const int32_t *d_indices, int64_t nnz, const float *d_dinv_table, int32_t max_deg, int32_t *d_cnt,
                          int32_t *d_deg, uint8_t *d_flags, float *d_values, void *stream);
 
+/* SEPT's per-epoch perturbed joint graph (model/ranking/SEPT.py:84-111, get_adj_mat(is_subgraph=True)) as two value arrays over a fixed
+ * structure: the sorted CSR pattern of R + R^T + F over the n_users + n_items nodes (R: the training rows, F: the pruned follow pairs at
+ * (follower, followee) only), which holds the non-zeros of every epoch's graph.  d_pos_ui / d_pos_iu [n_edges]: the CSR positions of a
+ * training row's two entries; d_pos_f [n_pairs]: the position of a follow pair's entry; d_keep_rows / d_keep_pairs: the kept rows and pairs
+ * (prefixes of the caller's permutations; duplicated rows and pairs add up).  d_keep_rows == NULL keeps every training row and
+ * d_keep_pairs == NULL (with n_keep_pairs == 0) no pair: the plain joint adjacency the reference returns for drop_rate <= 0 (:98-103).
+ * d_indptr [n + 1], d_row_of_nnz / d_indices [nnz]: the structure; d_pos_t [nnz]: where entry e sits in the CSR of the TRANSPOSED structure.
+ * An entry's weight a is its count in the rating blocks and count^2 in the user-user block; a node's degree is the sum of the weights of
+ * its ROW; value = fl32(fl32(dinv[deg_row] a) dinv[deg_col]), 0 for entries nothing was kept of, with d_dinv_table[k] = float32
+ * power(k, -0.5) for k = 0 .. max_deg (inf -> 0; made by the host with numpy; max_deg >= the full graph's largest weighted row sum).
+ * d_values [nnz]: M in the structure's order; d_values_t [nnz]: M^T in the transposed structure's order.  Scratch: d_cnt int32[nnz],
+ * d_deg int32[n_users + n_items].  Integer atomics only: bit-identical to the reference's scipy arithmetic, the same bits every run. */
+int qrec_sept_perturbed_values(const int32_t *d_pos_ui, const int32_t *d_pos_iu, int64_t n_edges, const int32_t *d_pos_f, int64_t n_pairs,
+                               const int32_t *d_keep_rows, int64_t n_keep_rows, const int32_t *d_keep_pairs, int64_t n_keep_pairs,
+                               int32_t n_users, int32_t n_items, const int64_t *d_indptr, const int32_t *d_row_of_nnz,
+                               const int32_t *d_indices, const int32_t *d_pos_t, int64_t nnz, const float *d_dinv_table, int32_t max_deg,
+                               int32_t *d_cnt, int32_t *d_deg, float *d_values, float *d_values_t, void *stream);
+
 /* ---- BUIR (model/ranking/BUIR.py) ------------------------------------------------------------------ *
  * The propagation of both encoders is qrec_spmm_csr on the epoch's two sub-graphs.  What the model adds:      */
 

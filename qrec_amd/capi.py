@@ -77,6 +77,7 @@ _SIGNATURES = {
     "qrec_mark_batch_rows": [_vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "qrec_bpr_batch_loss_grad": [_vp, _f32, _i32, _i64, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _i64, _vp],
     "qrec_subgraph_values": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "qrec_sept_perturbed_values": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "qrec_ordered_scatter_workspace_bytes": [_i64, _i32, _vp],
     "qrec_scatter_add_rows_ordered": [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp],
     "qrec_adam_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
@@ -848,6 +849,16 @@ def subgraph_values(d_u, d_i, d_pos_ui, d_pos_iu, n_edges: int, n_users: int, n_
     _check(load().qrec_subgraph_values(_dp(d_u), _dp(d_i), _dp(d_pos_ui), _dp(d_pos_iu), n_edges, n_users, n_items, _dp(d_keep_rows), n_keep,
                                        _dp(d_drop_users), n_drop_users, _dp(d_drop_items), n_drop_items, _dp(d_row_of_nnz), _dp(d_indices), nnz,
                                        _dp(d_dinv_table), max_deg, _dp(d_cnt), _dp(d_deg), _dp(d_flags), _dp(d_values), _sh(stream)))
+
+
+def sept_perturbed_values(d_pos_ui, d_pos_iu, n_edges: int, d_pos_f, n_pairs: int, n_users: int, n_items: int, d_indptr, d_row_of_nnz, d_indices,
+                          d_pos_t, nnz: int, d_dinv_table, max_deg: int, d_cnt, d_deg, d_values, d_values_t, d_keep_rows=None, n_keep_rows: int = 0,
+                          d_keep_pairs=None, n_keep_pairs: int = 0, stream=None):
+    """value arrays of SEPT's perturbed joint graph and of its transpose over the fixed union structure (include/qrec_hip.h, csrc/augment.hip)"""
+    _check(load().qrec_sept_perturbed_values(_dp(d_pos_ui), _dp(d_pos_iu), n_edges, _dp(d_pos_f), n_pairs, _dp(d_keep_rows), n_keep_rows,
+                                             _dp(d_keep_pairs), n_keep_pairs, n_users, n_items, _dp(d_indptr), _dp(d_row_of_nnz), _dp(d_indices),
+                                             _dp(d_pos_t), nnz, _dp(d_dinv_table), max_deg, _dp(d_cnt), _dp(d_deg), _dp(d_values), _dp(d_values_t),
+                                             _sh(stream)))
 
 
 class OrderedScatter:

@@ -21,6 +21,22 @@
 //                             table of numpy's own float32 power(k, -0.5) for k = 0 .. max degree: bit-identical to the reference's values.
 // Bytes per draw at the Yelp2018 shape: sort of 1.24 M keys + 2 x 1.24 M int atomics + 2.47 M values written: ~0.15 ms, against
 // 14 ms of host work per sub-graph in round 5.
+//
+// SEPT's perturbed joint graph (get_adj_mat(is_subgraph=True), model/ranking/SEPT.py:84-111; throughput mode of SEPT) is NOT a sub-graph of
+// the joint adjacency: besides the kept rating rows (both ways) it carries the kept follow pairs, counts squared, ONE way in the user-user
+// block, so its row sums are not edge counts and it is not symmetric (the backward pass needs M^T).  The scheme carries over with another
+// fixed structure -- the sorted CSR pattern of R + R^T + F (F: every pruned follow pair at (follower, followee)), built once on the host, which
+// holds the non-zeros of every epoch's graph -- and qrec_sept_perturbed_values:
+//   * sept_count_kernel    kept row t -> cnt[pos_ui[t]] += 1, cnt[pos_iu[t]] += 1; kept pair p -> cnt[pos_f[p]] += 1 (int atomics; duplicates add up)
+//   * sept_degree_kernel   deg[r] = sum over row r of the weights a = cnt (rating blocks) or cnt^2 (user-user block): a per-row pass over the
+//                          CSR, an integer, no atomics
+//   * sept_values_kernel   value[e] = cnt[e] ? fl32(fl32(dinv[deg[row e]] a) dinv[deg[col e]]) : 0 -- the ROW sum of the column node, as the
+//                          reference's D M D has it (a kept follow entry whose followee has an empty row is 0) -- written at e and, through a
+//                          host-made position map, at e's place in the CSR of the transposed structure: M and M^T from one pass, no float atomics.
+// Known cost, as for SGL / BUIR: the perturbed view's SpMM runs over the whole union structure, ~1 / (1 - drop_rate) of the kept entries
+// (1 / 0.7 at the stock -drop_rate 0.3).  Measured (tools/bench_sept_epoch.py, profiles/sept_throughput.json; the 0.15 ms / 14 ms above are
+// SGL's figures): Yelp2018 shape with 10 followees per user, d = 64: draw 0.59 ms against 69.9 + 36.6 ms of host work (replay + scipy, two plans +
+// upload) per joint epoch; the perturbed view's forward SpMM 80.2 us over the union structure against 64.5 us over the compact CSR (x 1.24).
 #include "common.h"
 
 using namespace qrec;
@@ -69,6 +85,61 @@ __global__ void subgraph_values_kernel(const int32_t *__restrict__ cnt, const in
     values[e] = v;
 }
 
+// ---- SEPT's perturbed joint graph (see the header comment) ---------------------------------------------------------------------
+// entry k < n_rows: a kept training row (keep_rows == nullptr: every row); n_rows <= k < n_rows + n_pairs_kept: a kept follow pair
+__global__ void sept_count_kernel(const int32_t *__restrict__ pos_ui, const int32_t *__restrict__ pos_iu, int64_t n_edges,
+                                  const int32_t *__restrict__ pos_f, int64_t n_pairs, const int32_t *__restrict__ keep_rows, int64_t n_rows,
+                                  const int32_t *__restrict__ keep_pairs, int64_t n_pairs_kept, int32_t *__restrict__ cnt) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n_rows) {
+        const int64_t t = keep_rows ? (int64_t)keep_rows[k] : k;
+        if (t < 0 || t >= n_edges) return;                    // a keep list is a prefix of a permutation of range(n_edges); never trust it past the arrays
+        atomicAdd(cnt + pos_ui[t], 1); atomicAdd(cnt + pos_iu[t], 1);
+    } else if (k < n_rows + n_pairs_kept) {
+        const int64_t p = keep_pairs[k - n_rows];
+        if (p < 0 || p >= n_pairs) return;
+        atomicAdd(cnt + pos_f[p], 1);
+    }
+}
+
+// an entry's weight: its count in the rating blocks, count^2 in the user-user block (social_mat.multiply(social_mat), SEPT.py:96)
+__device__ __forceinline__ int sept_weight(int c, int row, int col, int n_users) { return (row < n_users && col < n_users) ? c * c : c; }
+
+// deg[r] = sum of the weights of row r: 16 lanes per row over the CSR, an integer sum (exact in any order)
+__global__ void sept_degree_kernel(const int64_t *__restrict__ indptr, const int32_t *__restrict__ col_of, const int32_t *__restrict__ cnt,
+                                   int64_t n_nodes, int n_users, int32_t *__restrict__ deg) {
+    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const int lane = threadIdx.x & 15;
+    const bool live = r < n_nodes;
+    int s = 0;
+    if (live)
+        for (int64_t e = indptr[r] + lane, end = indptr[r + 1]; e < end; e += 16) s += sept_weight(cnt[e], (int)r, col_of[e], n_users);
+    for (int m = 8; m; m >>= 1) s += __shfl_xor(s, m, 16);
+    if (live && lane == 0) deg[r] = s;
+}
+
+// value[e] = fl32(fl32(dinv[deg[row e]] a) dinv[deg[col e]]) -- the ROW sum of the column node, D M D of a matrix that is not symmetric --
+// written at e and at e's place in the transposed structure's CSR
+__global__ void sept_values_kernel(const int32_t *__restrict__ cnt, const int32_t *__restrict__ deg, const int32_t *__restrict__ row_of,
+                                   const int32_t *__restrict__ col_of, const int32_t *__restrict__ pos_t, int64_t nnz, int n_users,
+                                   const float *__restrict__ dinv, int max_deg, float *__restrict__ values, float *__restrict__ values_t) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nnz) return;
+    const int c = cnt[e];
+    float v = 0.f;
+    if (c) {
+        const int r = row_of[e], cl = col_of[e];
+        const unsigned dr = (unsigned)deg[r], dc = (unsigned)deg[cl];
+        // the table covers the full graph's largest weighted row sum, which bounds every perturbed graph's; clamp instead of reading past it
+        const float a = dinv[dr < (unsigned)max_deg ? dr : (unsigned)max_deg], b = dinv[dc < (unsigned)max_deg ? dc : (unsigned)max_deg];
+        v = (a * (float)sept_weight(c, r, cl, n_users)) * b;
+    }
+    values[e] = v;
+    const int64_t t = pos_t[e];
+    if (t >= 0 && t < nnz) values_t[t] = v;
+}
+
 }  // namespace
 
 extern "C" {
@@ -109,6 +180,42 @@ int qrec_subgraph_values(const int32_t *d_u, const int32_t *d_i, const int32_t *
     if (nnz > 0) {
         hipLaunchKernelGGL(subgraph_values_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, d_cnt, d_deg, d_row_of_nnz, d_indices,
                            nnz, d_dinv_table, max_deg, d_values);
+        QREC_LAUNCH_CHECK();
+    }
+    return QREC_OK;
+}
+
+int qrec_sept_perturbed_values(const int32_t *d_pos_ui, const int32_t *d_pos_iu, int64_t n_edges, const int32_t *d_pos_f, int64_t n_pairs,
+                               const int32_t *d_keep_rows, int64_t n_keep_rows, const int32_t *d_keep_pairs, int64_t n_keep_pairs,
+                               int32_t n_users, int32_t n_items, const int64_t *d_indptr, const int32_t *d_row_of_nnz,
+                               const int32_t *d_indices, const int32_t *d_pos_t, int64_t nnz, const float *d_dinv_table, int32_t max_deg,
+                               int32_t *d_cnt, int32_t *d_deg, float *d_values, float *d_values_t, void *stream) {
+    QREC_REQUIRE(d_pos_ui && d_pos_iu && d_indptr && d_row_of_nnz && d_indices && d_pos_t && d_dinv_table && d_cnt && d_deg && d_values && d_values_t,
+                 "qrec_sept_perturbed_values: null argument");
+    QREC_REQUIRE(n_edges >= 0 && n_edges < ((int64_t)1 << 31) && n_pairs >= 0 && n_pairs < ((int64_t)1 << 31) && nnz >= 0 &&
+                     nnz < ((int64_t)1 << 31) && n_users >= 0 && n_items >= 0 && max_deg >= 0,
+                 "qrec_sept_perturbed_values: bad sizes (32-bit CSR positions: rows, pairs and non-zeros below 2^31)");
+    QREC_REQUIRE(n_pairs == 0 || d_pos_f, "qrec_sept_perturbed_values: null argument (follow pairs without their CSR positions)");
+    QREC_REQUIRE(n_keep_rows >= 0 && n_keep_rows <= n_edges, "qrec_sept_perturbed_values: bad keep list (more kept training rows than rows)");
+    QREC_REQUIRE(n_keep_pairs >= 0 && n_keep_pairs <= n_pairs && (n_keep_pairs == 0 || d_keep_pairs),
+                 "qrec_sept_perturbed_values: bad keep list (more kept follow pairs than pairs, or a count without its list)");
+    hipStream_t st = as_stream(stream);
+    const int64_t n_nodes = (int64_t)n_users + n_items;
+    const int64_t n_rows = d_keep_rows ? n_keep_rows : n_edges, n_fol = d_keep_pairs ? n_keep_pairs : 0;
+    if (nnz > 0) QREC_HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (size_t)nnz, st));
+    if (nnz > 0 && n_rows + n_fol > 0) {
+        hipLaunchKernelGGL(sept_count_kernel, dim3((unsigned)((n_rows + n_fol + 255) / 256)), dim3(256), 0, st, d_pos_ui, d_pos_iu, n_edges, d_pos_f,
+                           n_pairs, d_keep_rows, n_rows, d_keep_pairs, n_fol, d_cnt);
+        QREC_LAUNCH_CHECK();
+    }
+    if (n_nodes > 0) {
+        hipLaunchKernelGGL(sept_degree_kernel, dim3((unsigned)((n_nodes * 16 + 255) / 256)), dim3(256), 0, st, d_indptr, d_indices, d_cnt, n_nodes,
+                           n_users, d_deg);
+        QREC_LAUNCH_CHECK();
+    }
+    if (nnz > 0) {
+        hipLaunchKernelGGL(sept_values_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, d_cnt, d_deg, d_row_of_nnz, d_indices, d_pos_t,
+                           nnz, n_users, d_dinv_table, max_deg, d_values, d_values_t);
         QREC_LAUNCH_CHECK();
     }
     return QREC_OK;

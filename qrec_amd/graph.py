@@ -176,6 +176,92 @@ class SubgraphSampler:
         return out
 
 
+class SeptUnionStructure:
+    """Host side of SEPT's per-epoch perturbed joint graph on the device (get_adj_mat(is_subgraph=True), SEPT.py:84-111; the throughput mode of SEPT,
+    csrc/augment.hip).  The perturbed graph is not a sub-graph of the joint adjacency -- the kept follow pairs go, counts squared, one way
+    into the user-user block -- so the fixed structure is the sorted CSR pattern of R + R^T + F (F: every pruned follow pair at
+    (follower, followee)); every epoch's graph is a VALUE array over it, and its transpose a value array over the transposed structure.
+    Host work, once: the union structure (``indptr`` / ``indices``) and its transpose (``indptr_t`` / ``indices_t``), each training row's two
+    positions and each pair's one, the position of every entry in the transposed CSR, numpy's own float32 power(k, -0.5) table up to the
+    full graph's largest weighted row sum (rating count + sum of follow counts squared).  The trainer builds its two plans from the two
+    structures once (``SEPTTrainer.set_perturbed_structure``).  Pure numpy: no device is touched here (``SeptGraphSampler`` uploads)."""
+
+    def __init__(self, n_users: int, n_items: int, uid: np.ndarray, iid: np.ndarray, follower: np.ndarray, followee: np.ndarray):
+        self.nu, self.ni, self.n = int(n_users), int(n_items), int(n_users + n_items)
+        uid = np.asarray(uid, np.int64); iid = np.asarray(iid, np.int64)
+        fo = np.asarray(follower, np.int64); fe = np.asarray(followee, np.int64)
+        self.n_edges, self.n_pairs = int(uid.size), int(fo.size)
+        n = max(self.n, 1)
+        key_ui, key_iu, key_f = uid * n + (iid + self.nu), (iid + self.nu) * n + uid, fo * n + fe
+        keys = np.unique(np.concatenate([key_ui, key_iu, key_f]))              # ascending: rows ascending, columns ascending inside a row
+        self.nnz = int(keys.size)
+        if self.nnz >= 2 ** 31 or self.n_edges >= 2 ** 31 or self.n_pairs >= 2 ** 31:
+            raise ValueError("SeptUnionStructure: 32-bit CSR positions")
+        row_of, col_of = keys // n, keys % n
+        self.indptr = np.concatenate([[0], np.cumsum(np.bincount(row_of, minlength=self.n))]).astype(np.int64)
+        self.indices = col_of.astype(np.int32)
+        self.pos_ui, self.pos_iu, self.pos_f = (np.searchsorted(keys, k).astype(np.int32) for k in (key_ui, key_iu, key_f))
+        # the transposed structure: entry e = (r, c) of the union sits at pos_t[e] of the CSR of the pattern's transpose
+        order = np.argsort(col_of * n + row_of, kind="stable")
+        self.pos_t = np.empty(self.nnz, np.int32); self.pos_t[order] = np.arange(self.nnz, dtype=np.int32)
+        self.indptr_t = np.concatenate([[0], np.cumsum(np.bincount(col_of, minlength=self.n))]).astype(np.int64)
+        self.indices_t = row_of[order].astype(np.int32)
+        # the full graph's largest weighted row sum bounds every perturbed graph's: rating count + sum over followees of (follow count)^2
+        deg = np.bincount(np.concatenate([uid, iid + self.nu]), minlength=self.n).astype(np.int64)
+        if self.n_pairs:
+            pairs, mult = np.unique(key_f, return_counts=True)
+            deg[:self.nu] += np.bincount(pairs // n, weights=mult.astype(np.float64) ** 2, minlength=self.nu).astype(np.int64)[:self.nu]
+        self.max_deg = int(deg.max()) if deg.size else 0
+        if self.max_deg >= 2 ** 24:
+            raise ValueError("SeptUnionStructure: a weighted row sum beyond float32's exact integers")
+        with np.errstate(divide="ignore"):
+            dinv = np.power(np.arange(self.max_deg + 1, dtype=np.float32), -0.5)  # float32 ** python float -> float32: the reference's d_inv
+        dinv[np.isinf(dinv)] = 0.0
+        self.row_of, self.dinv = row_of.astype(np.int32), dinv.astype(np.float32)
+
+    def sizes(self, drop_rate: float):
+        """(kept training rows, kept follow pairs): SEPT.py:85,91's int() truncations of Python float products"""
+        return int(self.n_edges * (1 - drop_rate)), int(self.n_pairs * (1 - drop_rate))
+
+
+class SeptGraphSampler(SeptUnionStructure):
+    """``SeptUnionStructure`` resident on the device + the per-epoch draw: two device permutations (the exact-size random subsets of
+    random.sample, from the throughput mode's Philox stream) and qrec_sept_perturbed_values.
+
+    ``draw(drop_rate, seed, stream_id, out, out_t)`` -> (values of M, values of M^T); a function of (seed, stream_id) alone:
+      kept training rows = the first int(E (1 - rate)) entries of permutation(E; seed, stream_id),
+      kept follow pairs  = the first int(R (1 - rate)) entries of permutation(R; seed, stream_id + 1)          (SEPT.py:85,91)
+    ``drop_rate <= 0``: the plain joint adjacency, no follow entries (SEPT.py:98-103)."""
+
+    def __init__(self, n_users: int, n_items: int, uid: np.ndarray, iid: np.ndarray, follower: np.ndarray, followee: np.ndarray):
+        super().__init__(n_users, n_items, uid, iid, follower, followee)
+        up = DeviceBuffer.from_numpy
+        pad = lambda a: a if a.size else np.zeros(1, a.dtype)
+        self.d_pos_ui, self.d_pos_iu, self.d_pos_f = up(pad(self.pos_ui)), up(pad(self.pos_iu)), up(pad(self.pos_f))
+        self.d_indptr, self.d_row_of, self.d_indices = up(self.indptr), up(pad(self.row_of)), up(pad(self.indices))
+        self.d_pos_t, self.d_dinv = up(pad(self.pos_t)), up(self.dinv)
+        self.d_cnt, self.d_deg = DeviceBuffer(max(self.nnz, 1), np.int32), DeviceBuffer(max(self.n, 1), np.int32)
+        m = max(self.n_edges, self.n_pairs, 1)
+        self.scratch = DeviceBuffer(capi.random_permutations_scratch_bytes(m, 1), np.uint8)
+        self.d_keep, self.d_skeep = DeviceBuffer(max(self.n_edges, 1), np.int32), DeviceBuffer(max(self.n_pairs, 1), np.int32)
+
+    def draw(self, drop_rate: float, seed: int, stream_id: int, out: DeviceBuffer | None = None, out_t: DeviceBuffer | None = None, stream=None):
+        out = out if out is not None else DeviceBuffer(max(self.nnz, 1), np.float32)
+        out_t = out_t if out_t is not None else DeviceBuffer(max(self.nnz, 1), np.float32)
+        common = (self.d_pos_ui, self.d_pos_iu, self.n_edges, self.d_pos_f, self.n_pairs, self.nu, self.ni, self.d_indptr, self.d_row_of, self.d_indices,
+                  self.d_pos_t, self.nnz, self.d_dinv, self.max_deg, self.d_cnt, self.d_deg, out, out_t)
+        if drop_rate <= 0:
+            capi.sept_perturbed_values(*common, stream=stream)
+            return out, out_t
+        k, sk = self.sizes(drop_rate)
+        if self.n_edges:
+            capi.random_permutations(self.n_edges, 1, seed, stream_id, self.scratch, self.d_keep, None, stream)
+        if self.n_pairs:
+            capi.random_permutations(self.n_pairs, 1, seed, stream_id + 1, self.scratch, self.d_skeep, None, stream)
+        capi.sept_perturbed_values(*common, d_keep_rows=self.d_keep, n_keep_rows=k, d_keep_pairs=self.d_skeep, n_keep_pairs=sk, stream=stream)
+        return out, out_t
+
+
 def spectral_row_key(indptr: np.ndarray, indices: np.ndarray, values: np.ndarray, split_row: int, n_iter: int = 12,
                      seed: int = 0) -> np.ndarray:
     """A 1-D embedding of the nodes of a bipartite, symmetrically normalised adjacency in which the nodes of one community
@@ -1563,6 +1649,23 @@ class SEPTTrainer:
     def set_perturbed_graph(self, M):
         """the epoch's get_adj_mat(is_subgraph=True) (scipy CSR, N x N)"""
         self.aug.set_matrix(M, split_row=self.nu)
+
+    def set_perturbed_structure(self, indptr, indices, indptr_t, indices_t):
+        """throughput mode, once: the fixed union structure every epoch's perturbed graph lives in and its transpose
+        (``SeptUnionStructure``); the two plans are built here -- over the nodes of the joint graph, so with its row -> XCD-run
+        map -- and ``set_perturbed_values`` swaps their value arrays per epoch."""
+        chunk = self.pref.plan.row_chunk
+        kw = dict(split_row=self.nu, row_chunk=chunk) if chunk is not None else dict(split_row=self.nu, chunks=1)
+        zeros = np.zeros(np.size(indices), np.float32)
+        self._aug_plans = (SpmmPlan(np.asarray(indptr, np.int64), np.asarray(indices, np.int32), zeros, self.ld, **kw),
+                           SpmmPlan(np.asarray(indptr_t, np.int64), np.asarray(indices_t, np.int32), zeros, self.ld, **kw))
+
+    def set_perturbed_values(self, vals: DeviceBuffer, vals_t: DeviceBuffer):
+        """the epoch's perturbed graph drawn on the device (``SeptGraphSampler.draw``): values of M over the union structure, values
+        of M^T over the transposed one"""
+        if getattr(self, "_aug_plans", None) is None:
+            raise RuntimeError("set_perturbed_structure() first")
+        self.aug.plan, self.aug.planT = self._aug_plans[0].with_values(vals), self._aug_plans[1].with_values(vals_t)
 
     def _halve(self, stream=None):
         capi.scale_copy(self.E0, self.W, self.n * self.ld, 0.5, stream)

@@ -1,7 +1,8 @@
 """MHCN behind the reference's class name and hooks (model/ranking/MHCN.py:15-240): multi-channel hypergraph convolution
 over three motif-induced user-user graphs (social, joint, purchase) and the user-item graph, self-gated channel inputs,
 channel attention, and a hierarchical mutual-information loss per channel whose negatives are row / column shuffles.
-Needs the ``social`` file (``social.setup``); evaluated every epoch, best epoch kept."""
+Needs the ``social`` file (``social.setup``); evaluated every epoch, best epoch kept.  The batch stream is the reference's
+CPython stream, replayed on the host and uploaded (exact mode, default), or drawn on the device (``qrec.mode=throughput``)."""
 from __future__ import annotations
 
 import os
@@ -10,7 +11,6 @@ import numpy as np
 
 from ...base.graphRecommender import GraphRecommender
 from ...base.socialRecommender import SocialRecommender
-from ...capi import DeviceBuffer
 from ...graph import MHCNTrainer, mhcn_channel_graphs
 from ...util import config
 
@@ -54,10 +54,10 @@ class MHCN(SocialRecommender, GraphRecommender):
         tr = self.trainer
         dp = tr.dp = self.data_parallel()              # one process per GPU: a step = batch_size x world rows, this rank's share
         step = self.batch_size * (dp.world if dp else 1)
-        for epoch, (u, i, j) in enumerate(self.iter_epoch_samples(self.maxEpoch)):                  # base/deepRecommender.py:29-52
-            d_u, d_i, d_j = DeviceBuffer.from_numpy(u), DeviceBuffer.from_numpy(i), DeviceBuffer.from_numpy(j)
-            for n, s in enumerate(range(0, u.size, step)):
-                lo, B = self.step_share(dp, min(step, u.size - s))
+        # base/deepRecommender.py:29-52: the CPython stream replayed and uploaded (exact mode) or drawn on the device (throughput mode)
+        for epoch, (n_rows, d_u, d_i, d_j) in enumerate(self.iter_epoch_device_samples(self.maxEpoch)):
+            for n, s in enumerate(range(0, n_rows, step)):
+                lo, B = self.step_share(dp, min(step, n_rows - s))
                 tr.train_step_async(d_u.ptr + 4 * (s + lo), d_i.ptr + 4 * (s + lo), d_j.ptr + 4 * (s + lo), B)
                 if not quiet:
                     print(self.foldInfo, "training:", epoch + 1, "batch", n, "rec loss:", tr.losses()[0])
