@@ -1164,6 +1164,40 @@ int qrec_score_topk_sparse_row_sigmoid_bias(const float *d_W, const float *d_ite
                                             const int32_t *d_rated_items, const float *d_rated_vals, int32_t N, void *d_scratch,
                                             int32_t *d_ids_out, float *d_scores_out, void *stream);
 
+/* ---- APR (model/ranking/APR.py; csrc/apr.hip), fp32.  d_E = the joint [U; V] table ([n_rows][ld], item row = n_users + item,
+ * ld in {32, 64, 128}, d live columns, pad columns zero), d_D = the perturbations in the same layout.  For a triplet (u, i, j):
+ * x = p_u.(q_i - q_j), x' = (p_u+D_u).((q_i+D_i) - (q_j+D_j)), g = -sigma(-x), c' = -reg_adv sigma(-x').
+ *
+ * qrec_apr_perturb (APR.py:43-53, one Session.run of update_U and update_V on the feeds u, v, n): on return every row of d_D that
+ * this batch does not touch is zero and every touched row is eps * Gamma * rsqrt(max(|Gamma|^2, 1e-12)) (tf.nn.l2_normalize over the
+ * d live columns), Gamma being the gradient of reg_adv sum softplus(-x') w.r.t. D, read with d_D as the previous call left it:
+ *   user row:  sum over its u slots, ascending, of c' ((q_v+D_v) - (q_n+D_n))
+ *   item row:  (sum over its v slots of c' (p_u+D_u)) + (sum over its n slots of -c' (p_u+D_u)), each lookup's slots ascending first.
+ * With d_v == d_n elementwise every Gamma row is +-0 and d_D comes out exactly +0.  No float atomics: producer, one stable
+ * radix sort of (row, slot), one walk that adds, normalises and writes the row; same inputs, same bits.  Work per call is
+ * proportional to B and to the previous call's B, never to n_rows: d_touched (int32 [1 + touched_capacity], ZERO before the
+ * first call, kept by the caller between calls, touched_capacity >= 3 B) lists the rows the previous call wrote, which are
+ * cleared first.  B = 0 clears them and returns.  An index outside its table gives that triplet no row.
+ * Workspace: qrec_apr_perturb_workspace_bytes(B, ld).  h_stage_ms (HOST float[4], NULL in training): a measurement aid -- the call
+ * then records events around its stages, waits for the last and writes the device milliseconds of producer, clear, sort, walk.
+ *
+ * qrec_apr_batch_loss_grad (APR.py:56-64): d_loss (double[3]) is ACCUMULATED into: sum softplus(-x); reg (l2_loss(p_u) + l2_loss(q_i));
+ * reg_adv sum softplus(-x').  d_dE (pre-zeroed, [n_rows][ld]) receives
+ *   dE[u] += g (q_i-q_j) + reg p_u + c' ((q_i+D_i)-(q_j+D_j));  dE[nu+i] += g p_u + reg q_i + c' (p_u+D_u);  dE[nu+j] += -g p_u - c' (p_u+D_u)
+ * A null d_D or reg_adv = 0 is the pretraining step (no perturbed term, d_loss[2] untouched).  d_workspace NULL = throughput
+ * mode: float atomics on 64-byte segments and one fp64 atomic per block and term; a workspace of
+ * qrec_apr_step_workspace_bytes(B, ld) bytes = parity mode: every row's gradient is the sum of its lookups' slots in batch
+ * order, one lookup (u, i, j) at a time (qrec_scatter_add_rows_ordered's rule), the loss sums folded in a fixed tree.
+ * A triplet with an index outside its table contributes nothing. */
+int qrec_apr_perturb_workspace_bytes(int32_t B, int32_t ld, int64_t *bytes);
+int qrec_apr_perturb(const float *d_E, float *d_D, int32_t n_users, int64_t n_rows, int32_t d, int32_t ld, const int32_t *d_u,
+                     const int32_t *d_v, const int32_t *d_n, int32_t B, float reg_adv, float eps, int32_t *d_touched,
+                     int32_t touched_capacity, void *d_workspace, int64_t workspace_bytes, float *h_stage_ms, void *stream);
+int qrec_apr_step_workspace_bytes(int32_t B, int32_t ld, int64_t *bytes);
+int qrec_apr_batch_loss_grad(const float *d_E, const float *d_D, int32_t n_users, int64_t n_rows, int32_t d, int32_t ld,
+                             const int32_t *d_u, const int32_t *d_i, const int32_t *d_j, int32_t B, float reg, float reg_adv,
+                             float *d_dE, double *d_loss, void *d_workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

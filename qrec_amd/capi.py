@@ -212,6 +212,10 @@ _SIGNATURES = {
     "qrec_cfgan_read_slots": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp],
     "qrec_score_topk_sparse_row_sigmoid_bias_scratch_bytes": [_i32, _i32, _vp],
     "qrec_score_topk_sparse_row_sigmoid_bias": [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    "qrec_apr_perturb_workspace_bytes": [_i32, _i32, _vp],
+    "qrec_apr_perturb": [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _i32, _vp, _i64, _vp, _vp],
+    "qrec_apr_step_workspace_bytes": [_i32, _i32, _vp],
+    "qrec_apr_batch_loss_grad": [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _i64, _vp],
 }
 _RESTYPES = {"qrec_last_error": C.c_char_p, "qrec_ratings_rows": C.c_int64, "qrec_ratings_count": C.c_int32,
              "qrec_ratings_names_bytes": C.c_int64, "qrec_ratings_free": None}
@@ -889,6 +893,71 @@ def bpr_batch_loss_grad(d_S, div: float, n_users: int, n_rows: int, ld: int, d_u
     ws, nb = ordered.reserve(3 * B, ld) if ordered is not None else (0, 0)
     _check(load().qrec_bpr_batch_loss_grad(_dp(d_S), div, n_users, n_rows, ld, _dp(d_u), _dp(d_i), _dp(d_j), B,
                                            eps, reg, _dp(d_dE), _dp(d_loss), _dp(d_row_mask), ws, nb, _sh(stream)))
+
+
+def apr_perturb_workspace_bytes(B: int, ld: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_apr_perturb_workspace_bytes(B, ld, C.byref(out)))
+    return out.value
+
+
+def apr_step_workspace_bytes(B: int, ld: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_apr_step_workspace_bytes(B, ld, C.byref(out)))
+    return out.value
+
+
+class AprWorkspace:
+    """a workspace of csrc/apr.hip sized by ``query(B, ld)`` (apr_perturb_workspace_bytes / apr_step_workspace_bytes), one per
+    trainer and call, grown on demand"""
+
+    def __init__(self, query):
+        self.query, self.buf = query, None
+
+    def reserve(self, B: int, ld: int):
+        need = self.query(max(int(B), 1), ld)
+        if self.buf is None or self.buf.nbytes < need:
+            device_sync()                   # a launch in flight may still be using the old workspace
+            self.buf = DeviceBuffer(need, np.uint8)
+        return self.buf.ptr, self.buf.nbytes
+
+
+class AprTouchedRows:
+    """the rows of the perturbation tables the previous qrec_apr_perturb call wrote (int32 [1 + capacity], zero at first): what the
+    next call clears.  Grown on demand, the list carried over."""
+
+    def __init__(self, capacity: int = 0):
+        self.capacity = max(int(capacity), 0)
+        self.buf = DeviceBuffer.zeros(1 + self.capacity, np.int32)
+
+    def reserve(self, n_rows: int):
+        if n_rows > self.capacity:
+            device_sync()
+            old, self.capacity = self.buf, int(n_rows)
+            self.buf = DeviceBuffer.zeros(1 + self.capacity, np.int32)
+            memcpy_d2d(self.buf, old, old.nbytes)
+            device_sync()
+        return self.buf.ptr, self.capacity
+
+
+def apr_perturb(d_E, d_D, n_users: int, n_rows: int, d: int, ld: int, d_u, d_v, d_n, B: int, reg_adv: float, eps: float,
+                touched: "AprTouchedRows", workspace: "AprWorkspace", stream=None, stage_ms: "np.ndarray | None" = None):
+    """the perturbations of APR after one update on the feeds (u, v, n) (include/qrec_hip.h, csrc/apr.hip).  ``stage_ms`` (float32 [4],
+    measurements only): the call waits for the device and fills in the milliseconds of producer, clear, sort and walk"""
+    tp, cap = touched.reserve(3 * B)
+    ws, nb = workspace.reserve(B, ld) if B > 0 else (0, 0)
+    hp = _hp(_req(stage_ms, np.float32, "stage_ms")) if stage_ms is not None else None
+    _check(load().qrec_apr_perturb(_dp(d_E), _dp(d_D), n_users, n_rows, d, ld, _dp(d_u), _dp(d_v), _dp(d_n), B, reg_adv, eps, tp, cap,
+                                   ws, nb, hp, _sh(stream)))
+
+
+def apr_batch_loss_grad(d_E, d_D, n_users: int, n_rows: int, d: int, ld: int, d_u, d_i, d_j, B: int, reg: float, reg_adv: float,
+                        d_dE, d_loss, stream=None, ordered: "AprWorkspace | None" = None):
+    """APR's step on two objectives: d_loss (double[3]) and d_dE are accumulated into; ``d_D`` None = the pretraining step;
+    ``ordered`` = a workspace of apr_step_workspace_bytes (parity mode), None = float atomics"""
+    ws, nb = ordered.reserve(B, ld) if ordered is not None else (0, 0)
+    _check(load().qrec_apr_batch_loss_grad(_dp(d_E), _dp(d_D), n_users, n_rows, d, ld, _dp(d_u), _dp(d_i), _dp(d_j), B, reg, reg_adv,
+                                           _dp(d_dE), _dp(d_loss), ws, nb, _sh(stream)))
 
 
 def adam_step(d_theta, d_m, d_v, d_grad, n_elems: int, grad_scale: float, alpha: float, beta1: float = 0.9,

@@ -702,6 +702,66 @@ class BprTfTrainer:
         return split_joint(self.opt.applied_gradient(pad), self.nu, self.d)
 
 
+class AprTrainer:
+    """APR (model/ranking/APR.py:20-70) on the joint [U; V] pack: pretraining steps on softplus(-x) + the batch L2 of the looked-up
+    user and positive rows, then per batch a perturbation update (eps * l2_normalize of the adversarial gradient at the batch's rows,
+    zero elsewhere) followed by the step on both objectives.  ONE Adam across the two phases: the file builds ``train_adv`` from
+    ``self.optimizer`` (APR.py:67-70), so slots and beta powers carry over.  The perturbation tables are dense and never swept
+    (csrc/apr.hip); parity mode (``ordered_reductions()``) runs the step's gradient scatter in the reference's CPU order, the
+    perturbation pass is the same in both modes."""
+
+    def __init__(self, U0, V0, lr: float, reg: float, reg_adv: float, eps: float, max_batch: int = 0):
+        self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
+        self.n = self.nu + self.ni
+        self.ld = padded_ld(self.d, np.float32)
+        self.lr, self.reg, self.reg_adv, self.eps = lr, reg, reg_adv, eps
+        self.step_ws = capi.AprWorkspace(capi.apr_step_workspace_bytes) if getattr(_REDUCTIONS, "ordered", False) else None
+        self.perturb_ws = capi.AprWorkspace(capi.apr_perturb_workspace_bytes)
+        self.touched = capi.AprTouchedRows(3 * max_batch)
+        self.E = DeviceBuffer.from_numpy(pack_joint(U0, V0, self.ld))
+        self.D = DeviceBuffer.zeros((self.n, self.ld), np.float32)
+        self.opt = Adam(self.E, lr)
+        self.dE = DeviceBuffer.zeros((self.n, self.ld), np.float32)
+        self.d_loss = DeviceBuffer.zeros(3, np.float64)      # [sum softplus(-x), batch L2, regAdv sum softplus(-x')]
+
+    def _step(self, D, reg_adv, d_u, d_i, d_j, B, stream):
+        self.dE.fill_bytes(0, stream); self.d_loss.fill_bytes(0, stream)
+        capi.apr_batch_loss_grad(self.E, D, self.nu, self.n, self.d, self.ld, d_u, d_i, d_j, B, self.reg, reg_adv, self.dE, self.d_loss,
+                                 stream, ordered=self.step_ws)
+        self.opt.step(self.dE, stream=stream)
+
+    def pretrain_step_async(self, d_u, d_i, d_j, B: int, stream=None):
+        """``self.train`` (APR.py:68,109): minimize(total_loss)"""
+        self._step(None, 0.0, d_u, d_i, d_j, B, stream)
+
+    def perturb_async(self, d_u, d_v, d_n, B: int, stream=None):
+        """one run of [update_U, update_V] on the feeds (u, v, n) (APR.py:43-53,116-117)"""
+        capi.apr_perturb(self.E, self.D, self.nu, self.n, self.d, self.ld, d_u, d_v, d_n, B, self.reg_adv, self.eps, self.touched,
+                         self.perturb_ws, stream)
+
+    def adversarial_step_async(self, d_u, d_i, d_j, B: int, stream=None):
+        """``self.train_adv`` (APR.py:70,118): minimize(loss_adv) with the perturbations as they stand"""
+        self._step(self.D, self.reg_adv, d_u, d_i, d_j, B, stream)
+
+    def losses(self, stream=None):
+        """(sum softplus(-x), reg (l2_loss(p_u) + l2_loss(q_i)), regAdv sum softplus(-x')) of the last step"""
+        return tuple(float(x) for x in self.d_loss.numpy(stream))
+
+    def loss(self, stream=None) -> float:
+        """``total_loss`` after a pretraining step, ``loss_adv`` after an adversarial one"""
+        return float(sum(self.losses(stream)))
+
+    def tables(self):
+        return split_joint(self.E.numpy(), self.nu, self.d)
+
+    def perturbations(self):
+        return split_joint(self.D.numpy(), self.nu, self.d)
+
+    def gradients(self, before=None):
+        """what the last step handed to Adam; the L2 term is the batch's, inside the gradient (``before`` is not needed)"""
+        return split_joint(self.opt.applied_gradient(), self.nu, self.d)
+
+
 def unique_first_appearance(idx: np.ndarray) -> np.ndarray:
     """tf.unique(x)[0]: distinct values in order of first occurrence (SimGCL.py:61-64)."""
     _, first = np.unique(idx, return_index=True)
