@@ -974,6 +974,41 @@ int qrec_sorec_relation_pass(double *d_P, double *d_Z, int32_t d, int32_t ld, co
                              double *d_slots, void *stream);
 int qrec_loss_fold(double *d_running, const double *d_slots, int64_t n, void *stream);
 
+/* ---- LOCABAL and SocialFD (model/rating/{LOCABAL,SocialFD}.py): passes that carry a dense d x d matrix H, fp64, order-exact
+ * d_H is row-major [d][d] doubles in global memory; a launch keeps it in LDS ([d][d | 1]) and writes it back at the end.
+ * Supported width: d <= QREC_SOCIAL_H_MAX_D (H then takes 129 KiB of the CU's 160 KiB); a wider call returns
+ * QREC_ERR_UNSUPPORTED from all four entries and touches nothing.  Every step conflicts with every other through H, so ONE
+ * workgroup of n_waves wavefronts (1..QREC_SOCIAL_MAX_WAVES, 0 = chosen from d; never fewer than ceil(d / 64), one thread
+ * per column) walks a pass step by step and works side by side inside a step.  Sums over d terms are formed as partial sums over 16 consecutive terms, each added one term after the
+ * other, then added in chunk order; that association depends on d alone, so every n_waves gives the same bits, as do two
+ * launches.  No float atomics.  The metric products H.H^T + (H.H^T)^T (SocialFD.py:44) and H.H^T + H^T.H (:82) are never
+ * formed: (H.H^T).v is computed as H.(H^T.v).
+ * qrec_locabal_sgd_ordered: LOCABAL.py:50-67 in array order (one wavefront).  d_w_user [n_users]: W[user], or 0 for a user
+ *   in no relation (a real weight is > 0).  p, q are copies; a user with a weight gets the weighted update and then the
+ *   plain one (the reference's `else` is commented out).  *d_loss = sum of w*err^2 or err^2, added in row order.
+ * qrec_locabal_social_pass: LOCABAL.py:68-80 over the edges (d_edge_u, d_edge_k, d_edge_sim) in order: e = sim - (p^T H).q;
+ *   H += ((lr*alpha)*e)*(p_i*q_j); H -= (lr*regS)*H; P[u] += ((lr*alpha)*e)*(H q); P[k] += ((lr*alpha)*e)*(p^T H), both on
+ *   the new H and the old p (k == u: onto the row just written).  d_slots[edge] = alpha*e^2.
+ * qrec_socialfd_sgd_ordered: SocialFD.py:28-72 in array order, x = P[u] and y = Q[i] being VIEWS as in the reference.  The
+ *   bands are r > 0.7, r <= 0.5 (two branches: distance < 1, >= 1) and the rest; *d_loss adds err^2 and then the band's
+ *   term per rating.  Bu, Bi are updated with regU, regI as the reference does.
+ * qrec_socialfd_social_pass: SocialFD.py:74-86; step k is user d_step_user[k] (data.user order) with followees
+ *   d_fe_ids[d_fe_indptr[k] ..] in dict order: per followee the metric term to d_slots[edge], P[u] -= ((lr*eta)*beta)*delta
+ *   and H -= ((lr*eta)*beta)*(H*(w.w)).                                                                                    */
+#define QREC_SOCIAL_H_MAX_D 128
+int qrec_locabal_sgd_ordered(double *d_P, double *d_Q, int32_t d, int32_t ld, const double *d_w_user, const int32_t *d_u,
+                             const int32_t *d_i, const double *d_rating, int64_t n, double lr, double regU, double regI,
+                             double *d_loss, void *stream);
+int qrec_locabal_social_pass(double *d_P, double *d_H, int32_t d, int32_t ld, const int32_t *d_edge_u, const int32_t *d_edge_k,
+                             const double *d_edge_sim, int64_t n_edges, int32_t n_waves, double lr, double alpha, double regS,
+                             double *d_slots, void *stream);
+int qrec_socialfd_sgd_ordered(double *d_P, double *d_Q, double *d_Bu, double *d_Bi, double *d_H, int32_t d, int32_t ld,
+                              const int32_t *d_u, const int32_t *d_i, const double *d_rating, int64_t n, int32_t n_waves, double lr,
+                              double regU, double regI, double eta, double alpha, double global_mean, double *d_loss, void *stream);
+int qrec_socialfd_social_pass(double *d_P, double *d_H, int32_t d, int32_t ld, const int32_t *d_step_user, int64_t n_steps,
+                              const int64_t *d_fe_indptr, const int32_t *d_fe_ids, int32_t n_waves, double lr, double eta, double beta,
+                              double *d_slots, void *stream);
+
 /* ---- CDAE: model/ranking/CDAE.py (csrc/autoencoder.hip) -----------------------------------------------------------------
  * The denoising auto-encoder over a whole user row, evaluated only where the reference's dense batch x n_items arithmetic is
  * non-zero.  fp32; tables [rows][ld] with ld a multiple of 32 and columns [nh, ld) zero; the decoder weight is ITEM-MAJOR

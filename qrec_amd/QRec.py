@@ -22,7 +22,7 @@ def resolve_model(name: str):
             return getattr(importlib.import_module(f"qrec_amd.model.{pkg}.{name}"), name)
         except ModuleNotFoundError:
             continue
-    raise ImportError(f"model {name} is not provided by qrec_amd (hot-path models: BPR, TBPR, SBPR, BasicMF, PMF, SVD, SVDPlusPlus, EE, LightGCN, NGCF, SimGCL, SGL, BUIR, SEPT, MHCN, WRMF, UserKNN, ItemKNN, SlopeOne, SoRec, SoReg, SocialMF, RSTE, SREE, ExpoMF, SERec, CoFactor, DiffNet, DHCF, CDAE, IRGAN, CFGAN, APR)")
+    raise ImportError(f"model {name} is not provided by qrec_amd (hot-path models: BPR, TBPR, SBPR, BasicMF, PMF, SVD, SVDPlusPlus, EE, LightGCN, NGCF, SimGCL, SGL, BUIR, SEPT, MHCN, WRMF, UserKNN, ItemKNN, SlopeOne, SoRec, SoReg, SocialMF, RSTE, SREE, LOCABAL, SocialFD, ExpoMF, SERec, CoFactor, DiffNet, DHCF, CDAE, IRGAN, CFGAN, APR)")
 
 
 def _run_fold(results, model, order, spread=False):

@@ -183,6 +183,11 @@ _SIGNATURES = {
                               _vp],
     "qrec_sorec_relation_pass": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _f64, _f64, _f64, _vp, _vp],
     "qrec_loss_fold": [_vp, _vp, _i64, _vp],
+    "qrec_locabal_sgd_ordered": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _vp, _vp],
+    "qrec_locabal_social_pass": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _f64, _f64, _f64, _vp, _vp],
+    "qrec_socialfd_sgd_ordered": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _f64, _f64, _f64, _f64, _f64, _f64,
+                                  _vp, _vp],
+    "qrec_socialfd_social_pass": [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _f64, _f64, _f64, _vp, _vp],
     "qrec_cdae_workspace_bytes": [_i32, _i32, _vp],
     "qrec_cdae_encode": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "qrec_cdae_decode": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -1571,6 +1576,39 @@ def sorec_relation_pass(d_P, d_Z, d: int, ld: int, d_rel_u, d_rel_v, d_rel_t, d_
 def loss_fold(d_running, d_slots, n: int, stream=None):
     """*d_running += slots[0], += slots[1], ... one after the other"""
     _check(load().qrec_loss_fold(_dp(d_running), _dp(d_slots), n, _sh(stream)))
+
+
+# LOCABAL and SocialFD: passes that carry the dense d x d matrix H (fp64, row-major [d][d]); d > SOCIAL_H_MAX_D raises
+# QRecError ERR_UNSUPPORTED and touches nothing.  n_waves: 0 = chosen from d; every value gives the same bits.
+SOCIAL_H_MAX_D = 128
+
+
+def locabal_sgd_ordered(d_P, d_Q, d: int, ld: int, d_w_user, d_u, d_i, d_rating, n: int, lr: float, regU: float, regI: float, d_loss,
+                        stream=None):
+    """LOCABAL's rating pass in array order; d_w_user[u] = W[user] or 0; *d_loss = sum of w*err^2 or err^2"""
+    _check(load().qrec_locabal_sgd_ordered(_dp(d_P), _dp(d_Q), d, ld, _dp(d_w_user), _dp(d_u), _dp(d_i), _dp(d_rating), n, lr, regU, regI,
+                                           _dp(d_loss), _sh(stream)))
+
+
+def locabal_social_pass(d_P, d_H, d: int, ld: int, d_edge_u, d_edge_k, d_edge_sim, n_edges: int, lr: float, alpha: float, regS: float,
+                        d_slots, n_waves: int = 0, stream=None):
+    """LOCABAL's pass over the similarity edges in order; d_slots[edge] = alpha*e^2"""
+    _check(load().qrec_locabal_social_pass(_dp(d_P), _dp(d_H), d, ld, _dp(d_edge_u), _dp(d_edge_k), _dp(d_edge_sim), n_edges, n_waves, lr,
+                                           alpha, regS, _dp(d_slots), _sh(stream)))
+
+
+def socialfd_sgd_ordered(d_P, d_Q, d_Bu, d_Bi, d_H, d: int, ld: int, d_u, d_i, d_rating, n: int, lr: float, regU: float, regI: float,
+                         eta: float, alpha: float, global_mean: float, d_loss, n_waves: int = 0, stream=None):
+    """SocialFD's rating pass in array order; *d_loss = sum of err^2 and the band terms, in the reference's order"""
+    _check(load().qrec_socialfd_sgd_ordered(_dp(d_P), _dp(d_Q), _dp(d_Bu), _dp(d_Bi), _dp(d_H), d, ld, _dp(d_u), _dp(d_i), _dp(d_rating), n,
+                                            n_waves, lr, regU, regI, eta, alpha, global_mean, _dp(d_loss), _sh(stream)))
+
+
+def socialfd_social_pass(d_P, d_H, d: int, ld: int, d_step_user, n_steps: int, d_fe_indptr, d_fe_ids, lr: float, eta: float, beta: float,
+                         d_slots, n_waves: int = 0, stream=None):
+    """SocialFD's pass over every user's followees; d_slots[edge] = the metric term"""
+    _check(load().qrec_socialfd_social_pass(_dp(d_P), _dp(d_H), d, ld, _dp(d_step_user), n_steps, _dp(d_fe_indptr), _dp(d_fe_ids), n_waves,
+                                            lr, eta, beta, _dp(d_slots), _sh(stream)))
 
 
 # ---- CDAE (csrc/autoencoder.hip; the list format is described in include/qrec_hip.h) ----------------------------------------

@@ -714,6 +714,96 @@ class SocialSgd:
         return self.mf.biases()
 
 
+class SocialHSgd:
+    """LOCABAL and SocialFD on the device, order-exact, fp64 (model/rating/{LOCABAL,SocialFD}.py): the two social models
+    whose passes carry a dense d x d matrix H.  Holds P, Q (``tables``), H, LOCABAL's per-user weight array (``W``: 0 for a
+    user in no relation) or SocialFD's biases, and the walk of the social pass (``steps``: a social.Edges for LOCABAL, a
+    social.UserSteps in data.user order for SocialFD).  Every step rewrites H, so there is no schedule: one workgroup
+    walks a pass step by step (social.hip).  ``rating_pass`` then ``social_pass`` as in :class:`SocialSgd`: the social
+    pass' loss terms are added onto the running loss one by one in walk order; ``sumsq_terms`` includes sum H^2.
+    ``n_waves``: wavefronts of the workgroup, 0 = chosen from d; the results do not depend on it."""
+    KINDS = ("LOCABAL", "SocialFD")
+
+    def __init__(self, tables: DeviceTables, n: int, kind: str, steps, H, W=None, Bu=None, Bi=None, n_waves: int = 0):
+        if kind not in self.KINDS:
+            raise ValueError(f"unknown model {kind!r}")
+        if tables.dtype != np.float64:
+            raise ValueError("the social models run on fp64 tables")
+        if tables.d > capi.SOCIAL_H_MAX_D:
+            raise ValueError(f"{kind} supports num.factors <= {capi.SOCIAL_H_MAX_D} (the d x d matrix H stays in LDS), got {tables.d}")
+        self.t, self.n, self.kind, self.steps, self.n_waves = tables, n, kind, steps, n_waves
+        up = lambda a, dt: DeviceBuffer.from_numpy(np.ascontiguousarray(a, dtype=dt) if np.size(a) else np.zeros(1, dt))
+        H = np.ascontiguousarray(H, dtype=np.float64)
+        assert H.shape == (tables.d, tables.d)
+        self.d_H = DeviceBuffer.from_numpy(H)
+        self.d_u = DeviceBuffer(max(n, 1), np.int32); self.d_i = DeviceBuffer(max(n, 1), np.int32)
+        self.d_r = DeviceBuffer(max(n, 1), np.float64)
+        self.d_stats = DeviceBuffer.zeros(6, np.float64)             # loss, sum P^2, Q^2, H^2, Bu^2, Bi^2
+        self.d_Bu = self.d_Bi = self.d_W = None
+        if kind == "LOCABAL":
+            assert np.size(W) == tables.n_users
+            self.d_W = up(W, np.float64)
+            self.d_eu, self.d_ek, self.d_es = up(steps.u, np.int32), up(steps.k, np.int32), up(steps.sim, np.float64)
+            self.n_steps = self.n_slots = steps.n
+        else:
+            self.d_Bu, self.d_Bi = up(Bu, np.float64), up(Bi, np.float64)
+            self.d_user, self.d_fe_ptr, self.d_fe_ids = up(steps.user, np.int32), up(steps.fe_ptr, np.int64), up(steps.fe_ids, np.int32)
+            self.n_steps = steps.n_steps
+            self.n_slots = int(steps.fe_ptr[-1]) if self.n_steps else 0
+        self.d_slots = DeviceBuffer(max(self.n_slots, 1), np.float64)
+
+    def rating_pass(self, u, i, r, lr: float, regU: float, regI: float, eta: float = 0.0, alpha: float = 0.0,
+                    global_mean: float = 0.0, stream=None) -> float:
+        """one pass over the ratings in the given (current trainingData) order; returns its loss (SocialFD: err^2 and the
+        band term per rating, in that order)"""
+        if self.n:                                       # no rows: nothing to upload, the pass is a no-op with loss 0
+            self.d_u.upload(np.ascontiguousarray(u, dtype=np.int32), stream)
+            self.d_i.upload(np.ascontiguousarray(i, dtype=np.int32), stream)
+            self.d_r.upload(np.ascontiguousarray(r, dtype=np.float64), stream)
+        t = self.t
+        if self.kind == "LOCABAL":
+            capi.locabal_sgd_ordered(t.P, t.Q, t.d, t.ld, self.d_W, self.d_u, self.d_i, self.d_r, self.n, lr, regU, regI, self.d_stats,
+                                     stream)
+        else:
+            capi.socialfd_sgd_ordered(t.P, t.Q, self.d_Bu, self.d_Bi, self.d_H, t.d, t.ld, self.d_u, self.d_i, self.d_r, self.n, lr, regU,
+                                      regI, eta, alpha, global_mean, self.d_stats, self.n_waves, stream)
+        return float(self.d_stats.head(1, stream)[0])
+
+    def social_pass(self, lr: float, alpha: float = 0.0, regS: float = 0.0, eta: float = 0.0, beta: float = 0.0,
+                    start: float | None = None, stream=None) -> float:
+        """the social half of the epoch (LOCABAL: alpha, regS; SocialFD: eta, beta); its loss terms are added one by one
+        in walk order onto the running loss -- the rating pass' loss, or ``start`` when given -- and that sum is returned"""
+        t = self.t
+        if start is not None:
+            self.d_stats.upload_head(np.array([start], dtype=np.float64), stream)
+        if self.kind == "LOCABAL":
+            capi.locabal_social_pass(t.P, self.d_H, t.d, t.ld, self.d_eu, self.d_ek, self.d_es, self.n_steps, lr, alpha, regS,
+                                     self.d_slots, self.n_waves, stream)
+        else:
+            capi.socialfd_social_pass(t.P, self.d_H, t.d, t.ld, self.d_user, self.n_steps, self.d_fe_ptr, self.d_fe_ids, lr, eta, beta,
+                                      self.d_slots, self.n_waves, stream)
+        capi.loss_fold(self.d_stats, self.d_slots, self.n_slots, stream)
+        return float(self.d_stats.head(1, stream)[0])
+
+    def sumsq_terms(self, stream=None):
+        """(sum P^2, sum Q^2, sum H^2, sum Bu^2 or 0, sum Bi^2 or 0)"""
+        t = self.t
+        capi.sumsq(t.P, t.code, t.n_users, t.d, t.ld, self.d_stats.ptr + 8, stream)
+        capi.sumsq(t.Q, t.code, t.n_items, t.d, t.ld, self.d_stats.ptr + 16, stream)
+        capi.sumsq(self.d_H, t.code, t.d, t.d, t.d, self.d_stats.ptr + 24, stream)
+        if self.d_Bu is not None:
+            capi.sumsq(self.d_Bu, t.code, t.n_users, 1, 1, self.d_stats.ptr + 32, stream)
+            capi.sumsq(self.d_Bi, t.code, t.n_items, 1, 1, self.d_stats.ptr + 40, stream)
+        s = self.d_stats.numpy(stream)
+        return tuple(float(x) for x in s[1:6])
+
+    def H(self):
+        return self.d_H.numpy().astype(np.float64)
+
+    def biases(self):
+        return self.d_Bu.numpy().astype(np.float64), self.d_Bi.numpy().astype(np.float64)
+
+
 class SvdppSgd:
     """SVD++ on the device, order-exact (model/rating/SVDPlusPlus.py:25-62): P, Q, the implicit-feedback table Y and
     the biases stay resident; ``rated`` = every user's train items in ``data.userRated`` order."""

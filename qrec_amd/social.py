@@ -1,5 +1,6 @@
-"""Host side of the social-trust rating models (model/rating/{SoRec,SoReg,SocialMF,RSTE,SREE}.py): the walk orders of their
-social passes as index arrays, and the level schedule the device runs them by.
+"""Host side of the social-trust rating models (model/rating/{SoRec,SoReg,SocialMF,RSTE,SREE,LOCABAL,SocialFD}.py): the walk
+orders of their social passes as index arrays, and the level schedule the device runs the first five by (LOCABAL and
+SocialFD carry a d x d matrix every step rewrites: nothing to schedule, their passes run step by step).
 
 The orders are fixed for a whole run -- ``social.user`` (first appearance in the relation file) for the per-user passes,
 the pruned ``social.relation`` list for SoRec -- so the schedule is built once per model instance.  A step reads and
@@ -166,6 +167,96 @@ def sorec_relations(rec) -> Relations:
                      np.asarray(w, dtype=np.float64))
 
 
+def socialfd_steps(rec) -> UserSteps:
+    """SocialFD's walk (SocialFD.py:74-80): :func:`user_steps` over ``data.user`` (id) order instead of ``social.user``;
+    a user without followees is a step with no edges"""
+    data, social = rec.data, rec.social
+    users, fe = [], []
+    for name, k in data.user.items():
+        users.append(k)
+        fol = social.getFollowees(name)
+        fe.append([(data.user[f], fol[f]) for f in fol if data.containsUser(f)])
+    return UserSteps(np.asarray(users, dtype=np.int32), *_csr(fe))
+
+
+def pagerank_ranks(relation_pairs) -> dict:
+    """{node: 1-based rank} by descending PageRank, as ``nx.pagerank(G, alpha=0.85)`` of the DiGraph of the pairs followed by a
+    stable descending sort gives it (LOCABAL.py:26-31): nodes in order of first appearance, unit edge weights with parallel
+    edges collapsed, the adjacency matrix row-normalised, uniform start and teleport vectors, the dangling nodes' mass
+    spread uniformly, at most 100 iterations, stopped by an L1 change below N * 1e-6; ties keep node order."""
+    import scipy.sparse as sp
+    index = {}
+    for a, b in relation_pairs:
+        for x in (a, b):
+            if x not in index:
+                index[x] = len(index)
+    n = len(index)
+    if n == 0:
+        return {}
+    rows = np.fromiter((index[a] for a, _ in relation_pairs), dtype=np.int64)
+    cols = np.fromiter((index[b] for _, b in relation_pairs), dtype=np.int64)
+    A = sp.csr_matrix((np.ones(rows.size), (rows, cols)), shape=(n, n))       # duplicates are summed ...
+    A.data[:] = 1.0                                                           # ... and collapse to one unit edge
+    S = np.asarray(A.sum(axis=1)).ravel()
+    S[S != 0] = 1.0 / S[S != 0]
+    A = sp.diags(S).tocsr() @ A
+    x = np.repeat(1.0 / n, n)
+    p = x.copy()
+    dangling = np.where(S == 0)[0]
+    for _ in range(100):
+        last = x
+        x = 0.85 * (A.T @ last + sum(last[dangling]) * p) + (1 - 0.85) * p
+        if np.absolute(x - last).sum() < n * 1e-6:
+            break
+    else:
+        raise RuntimeError("pagerank_ranks: the power iteration did not converge within 100 iterations")
+    nodes = list(index)
+    by_value = sorted(range(n), key=lambda k: float(x[k]), reverse=True)
+    rank = {k: r + 1 for r, k in enumerate(by_value)}
+    return {nodes[k]: rank[k] for k in range(n)}
+
+
+@dataclass
+class Edges:
+    """LOCABAL's social pass: edge t = (user u[t], friend k[t], cosine sim[t]) in the walk order of its S dict"""
+    u: np.ndarray
+    k: np.ndarray
+    sim: np.ndarray
+
+    @property
+    def n(self) -> int:
+        return int(self.u.size)
+
+
+def locabal_weights(rec) -> np.ndarray:
+    """W of LOCABAL.py:26-34 as an array over user ids: 1 / (1 + log(rank)) for a user of the pruned relation list, 0 for
+    every other user (a real weight is positive)"""
+    import math
+    ranks = pagerank_ranks([(r[0], r[1]) for r in rec.social.relation])
+    w = np.zeros(len(rec.data.user), dtype=np.float64)
+    for name, rank in ranks.items():
+        w[rec.data.user[name]] = 1 / (1 + math.log(rank))
+    return w
+
+
+def locabal_edges(rec, sim=None) -> Edges:
+    """S of LOCABAL.py:35-44 as its walk (:68-69): the outer dict's insertion order, then the inner dict's; a repeated
+    relation overwrites its value in place.  ``sim(relation line)``: the edge's value (default: cosine_sp of the two
+    users' rating dicts)"""
+    from .util.qmath import cosine_sp
+    data = rec.data
+    if sim is None:
+        sim = lambda line: cosine_sp(data.trainSet_u[line[0]], data.trainSet_u[line[1]])
+    S = {}
+    for line in rec.social.relation:
+        u1, u2 = line[0], line[1]
+        if data.containsUser(u1) and data.containsUser(u2):
+            S.setdefault(u1, {})[u2] = sim(line)
+    walk = [(data.user[a], data.user[b], float(S[a][b])) for a in S for b in S[a]]
+    return Edges(np.asarray([a for a, _, _ in walk], dtype=np.int32), np.asarray([b for _, b, _ in walk], dtype=np.int32),
+                 np.asarray([s for _, _, s in walk], dtype=np.float64))
+
+
 def followee_csr_by_user(rec):
     """RSTE: every training user's (id order) followees in dict order, their weights, and the weight sum as RSTE.py:47-54
     forms it (``np.array(weights).sum()``)"""
@@ -182,7 +273,7 @@ def followee_csr_by_user(rec):
 
 def synthetic_graph_steps(kind: str, n_users: int, follower, followee, weight):
     """The walk of model ``kind`` for a relation list over user ids 0 .. n_users-1 that all train (benchmarks and tests);
-    SoReg's Sim of an edge is taken to be its trust weight."""
+    SoReg's Sim and LOCABAL's cosine of an edge are taken to be its trust weight.  LOCABAL: (Edges, the weight array W)."""
     from types import SimpleNamespace
 
     from .data.social import Social
@@ -191,6 +282,10 @@ def synthetic_graph_steps(kind: str, n_users: int, follower, followee, weight):
     rec = SimpleNamespace(data=data, social=social)
     if kind == "SoRec":
         return sorec_relations(rec)
+    if kind == "SocialFD":
+        return socialfd_steps(rec)
+    if kind == "LOCABAL":
+        return locabal_edges(rec, sim=lambda line: float(line[2])), locabal_weights(rec)
     if kind == "RSTE":
         return followee_csr_by_user(rec)
     if kind == "SoReg":

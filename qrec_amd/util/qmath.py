@@ -1,4 +1,4 @@
-"""Host math helpers (util/qmath.py:58-76,127-146)."""
+"""Host math helpers (util/qmath.py:19-32,58-76,127-146)."""
 from __future__ import annotations
 
 import heapq
@@ -43,3 +43,18 @@ def pearson_sp(x1: dict, x2: dict) -> float:
         return total / (sqrt(denom1) * sqrt(denom2))
     except ZeroDivisionError:
         return 1 if overlapped else 0
+
+
+def cosine_sp(x1: dict, x2: dict) -> float:
+    """Cosine of two rating dicts over their common keys only -- both norms run over the overlap, not over the whole
+    dicts (util/qmath.py:19-32): summed in x1's key order, squares by Python's ``** 2``; no overlap gives 0."""
+    total = denom1 = denom2 = 0
+    try:
+        for k in x1:
+            if k in x2:
+                total += x1[k] * x2[k]
+                denom1 += x1[k] ** 2
+                denom2 += x2[k] ** 2
+        return total / (sqrt(denom1) * sqrt(denom2))
+    except ZeroDivisionError:
+        return 0

@@ -7,6 +7,14 @@ Epinions-like shape (40,000 users, 140,000 items, 660,000 ratings, 490,000 trust
 model and epoch: the rating pass and the social pass (each call ends in a device synchronisation), the social pass'
 level count and mean width; the social pass again at width 1 (social.sequential_schedule) on the same tables; and at
 FilmTrust the one-core numpy host mirror (tests/social_mirror.py) of both passes.
+
+    python tools/bench_social.py --locabal-fd [out.json]      # default out: profiles/locabal_fd_bench.json
+
+LOCABAL and SocialFD (engine.SocialHSgd; their passes carry a d x d matrix, one workgroup walks them step by step) at the
+same two workloads, d = 10 and d = 64: the rating pass and the social pass per epoch as the median of the same repeat
+count, microseconds per step (a rating; a similarity edge or followee edge), and beside them the one-core numpy mirror
+(tests/locabal_fd_mirror.py) in microseconds per step over the first MIRROR_STEPS steps of each pass; then, at FilmTrust and
+d = 10, 64, 128, the same passes with 1, 2, 4, 8 and 16 wavefronts in the workgroup (the results do not depend on it).
 """
 import json
 import os
@@ -118,7 +126,124 @@ def mirror_filmtrust(kind, wl, d=10, seed=0):
     return t1 - t0, time.perf_counter() - t1
 
 
+H_MODELS = ("LOCABAL", "SocialFD")
+H_DIMS = (10, 64)
+MIRROR_STEPS = 20_000
+SWEEP_DIMS = (10, 64, 128)
+SWEEP_WAVES = (1, 2, 4, 8, 16)
+
+
+def h_inputs(kind, wl, d, seed=0):
+    """tables scaled so that a whole pass at either shape stays finite: ratings in (0, 1], distances under H around 1"""
+    rng = np.random.default_rng(seed)
+    U, I = wl["U"], wl["I"]
+    r = wl["r"] / wl["r"].max()
+    P, Q = rng.random((U, d)) / 3, rng.random((I, d)) / 3
+    if kind == "SocialFD":
+        return dict(r=r, P=P / 10, Q=Q / 10, H=rng.random((d, d)) * 2 / d, Bu=rng.random(U) / 5, Bi=rng.random(I) / 5)
+    return dict(r=r, P=P, Q=Q, H=rng.random((d, d)) / d)
+
+
+def bench_h_model(kind, wl, d, n_waves=0):
+    from qrec_amd.engine import DeviceTables, SocialHSgd
+    from qrec_amd.social import synthetic_graph_steps
+    x = h_inputs(kind, wl, d)
+    t0 = time.perf_counter()
+    steps = synthetic_graph_steps(kind, wl["U"], wl["a"], wl["b"], wl["w"])
+    host_steps_s = time.perf_counter() - t0
+    t = DeviceTables(x["P"], x["Q"], np.float64)
+    if kind == "LOCABAL":
+        edges, W = steps
+        s = SocialHSgd(t, wl["u"].size, kind, edges, x["H"], W=W, n_waves=n_waves)
+    else:
+        s = SocialHSgd(t, wl["u"].size, kind, steps, x["H"], Bu=x["Bu"], Bi=x["Bi"], n_waves=n_waves)
+    lr = 0.001
+    rating, social = [], []
+    for _ in range(EPOCHS):
+        t0 = time.perf_counter()
+        s.rating_pass(wl["u"], wl["i"], x["r"], lr, 0.01, 0.01, 0.1, 0.3, 0.5)
+        t1 = time.perf_counter()
+        s.social_pass(lr, alpha=0.4, regS=0.01, eta=0.1, beta=0.1)
+        t2 = time.perf_counter()
+        rating.append(t1 - t0); social.append(t2 - t1)
+    P, Q = t.download()
+    rm, sm = float(np.median(rating)), float(np.median(social))
+    return dict(model=kind, d=d, host_steps_s=round(host_steps_s, 3), n_ratings=int(wl["u"].size), n_social_edges=int(s.n_slots),
+                rating_pass_ms=round(1e3 * rm, 3), social_pass_ms=round(1e3 * sm, 3),
+                rating_us_per_step=round(1e6 * rm / max(wl["u"].size, 1), 3), social_us_per_step=round(1e6 * sm / max(s.n_slots, 1), 3),
+                rating_pass_ms_all=[round(1e3 * v, 3) for v in rating], social_pass_ms_all=[round(1e3 * v, 3) for v in social],
+                finite=bool(np.isfinite(P).all() and np.isfinite(Q).all() and np.isfinite(s.H()).all()))
+
+
+def mirror_h_model(kind, wl, d):
+    """the one-core numpy mirror over the first MIRROR_STEPS steps of each pass: (rating us / step, social us / step)"""
+    import locabal_fd_mirror as L
+    from qrec_amd.social import synthetic_graph_steps
+    x = h_inputs(kind, wl, d)
+    P, Q, H = x["P"].copy(), x["Q"].copy(), x["H"].copy()
+    n = min(MIRROR_STEPS, wl["u"].size)
+    rows = list(zip(wl["u"][:n].tolist(), wl["i"][:n].tolist(), x["r"][:n].tolist()))
+    steps = synthetic_graph_steps(kind, wl["U"], wl["a"], wl["b"], wl["w"])
+    if kind == "LOCABAL":
+        edges, W = steps
+        walk = list(zip(edges.u[:MIRROR_STEPS].tolist(), edges.k[:MIRROR_STEPS].tolist(), edges.sim[:MIRROR_STEPS].tolist()))
+        t0 = time.perf_counter()
+        L.rating_locabal(P, Q, W, rows, 0.001, 0.01, 0.01)
+        t1 = time.perf_counter()
+        L.social_locabal(P, H, walk, 0.001, 0.4, 0.01, np.zeros(len(walk)))
+        m = len(walk)
+    else:
+        walk, m = [], 0
+        for k, u in enumerate(steps.user.tolist()):
+            fol = steps.fe_ids[steps.fe_ptr[k]:steps.fe_ptr[k + 1]].tolist()[:MIRROR_STEPS - m]
+            walk.append((u, fol)); m += len(fol)
+            if m >= MIRROR_STEPS:
+                break
+        Bu, Bi = x["Bu"].copy(), x["Bi"].copy()
+        t0 = time.perf_counter()
+        L.rating_socialfd(P, Q, Bu, Bi, H, rows, 0.001, 0.01, 0.01, 0.1, 0.3, 0.5)
+        t1 = time.perf_counter()
+        L.social_socialfd(P, H, walk, 0.001, 0.1, 0.1, np.zeros(m))
+    t2 = time.perf_counter()
+    return 1e6 * (t1 - t0) / max(n, 1), 1e6 * (t2 - t1) / max(m, 1)
+
+
+def main_locabal_fd(out_path):
+    from qrec_amd import capi
+    capi.init(0)
+    res = dict(device=capi.device_info()["arch"], repeats=EPOCHS, mirror_steps_timed=MIRROR_STEPS, workloads={})
+    for name, wl in (("filmtrust", filmtrust()), ("epinions_like", epinions_like())):
+        rows = []
+        for kind in H_MODELS:
+            for d in H_DIMS:
+                r = bench_h_model(kind, wl, d)
+                mr, ms = mirror_h_model(kind, wl, d)
+                r["host_mirror_rating_us_per_step"], r["host_mirror_social_us_per_step"] = round(mr, 2), round(ms, 2)
+                rows.append(r)
+                print(name, json.dumps(r), flush=True)
+        res["workloads"][name] = dict(n_users=wl["U"], n_items=wl["I"], n_ratings=int(wl["u"].size), n_relations=int(wl["a"].size),
+                                      models=rows)
+    # the same passes at FilmTrust under every workgroup size (a workgroup never has fewer than ceil(d / 64) wavefronts)
+    wl, sweep = filmtrust(), []
+    for kind in H_MODELS:
+        for d in SWEEP_DIMS:
+            for nw in SWEEP_WAVES:
+                r = bench_h_model(kind, wl, d, nw)
+                row = dict(model=kind, d=d, n_waves=max(nw, (d + 63) // 64), social_us_per_step=r["social_us_per_step"])
+                if kind == "SocialFD":
+                    row["rating_us_per_step"] = r["rating_us_per_step"]
+                sweep.append(row)
+                print("wave_sweep", json.dumps(row), flush=True)
+    res["wave_sweep_filmtrust"] = sweep
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", out_path)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--locabal-fd":
+        return main_locabal_fd(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "locabal_fd_bench.json"))
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "social_bench.json")
     from qrec_amd import capi
     capi.init(0)
