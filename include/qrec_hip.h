@@ -643,6 +643,8 @@ int qrec_sbpr_sgd_ordered(void *d_P, void *d_Q, const void *d_bias, int dtype, i
 
 /* ---- MHCN: model/ranking/MHCN.py:93-216 (self-gating, channel attention, hierarchical self-supervision) ---------------
  * Tables [rows][ld] fp32, ld in {32, 64, 128, 256}, columns >= d zero; d x d weights zero-padded to [ld][ld], biases [ld].
+ * qrec_gate_fwd / _bwd serve ld in {32, 64, 128} only: they stage the whole [ld][ld] weight matrix in LDS, and 256 KiB at
+ *   ld = 256 is more than a CU has.  Stride 256 is refused with a message; the attention and hss entry points keep it.
  * qrec_gate_fwd:  Y = X * sigmoid(X W + b), S = sigmoid(.)  -- self_gating / self_supervised_gating (MHCN.py:109-112).
  * qrec_gate_bwd:  Q = (dy_scale dY) * X * S (1 - S);  dX (+)= dy_scale dY * S + Q W^T.  The weight gradients are
  *   dW = X^T Q, db = column sums of Q: qrec_buir_wgrad(X, Q, ...).

@@ -2,6 +2,8 @@
 // hierarchical mutual-information loss, forward and backward.  All tables are [rows][ld] fp32, ld in {32, 64, 128, 256},
 // columns >= d zero; one group of LPR = ld/4 lanes per row, float4 per lane.  The d x d products (2 n d^2 FLOP, a few
 // hundred MFLOP per step) run on the vector ALUs with the weight matrix in LDS: they are bound by streaming the rows.
+// The two gate kernels stage all ld x ld floats of it, so they stop at ld = 128 (64 KiB; 256 KiB at ld = 256 is more than a
+// CU's 160 KiB of LDS) and qrec_gate_fwd / _bwd refuse stride 256; attention and the MIM loss hold no such state and keep it.
 //
 //   gate_fwd_kernel      Y = X * sigmoid(X W + b), S = sigmoid(.)                       MHCN.py:109-112
 //   gate_bwd_kernel      Q = dY * X * S(1-S);  dX (+)= dY * S + Q W^T   (dW = X^T Q, db = colsum Q: qrec_buir_wgrad)
@@ -388,17 +390,24 @@ int launch_rows(int64_t n) {
         case 256: { constexpr int LPR = 64; CALL; } break;                                                               \
         default: set_error(NAME ": row stride must be 32, 64, 128 or 256 floats (got %d)", ld); return QREC_ERR_INVALID; \
     }
+// the gates stage ld x ld floats in LDS: no stride 256 (their entry points have refused every other stride before this)
+#define QREC_MHCN_GATE_LD_SWITCH(CALL)                                                                                   \
+    switch (ld) {                                                                                                        \
+        case 32: { constexpr int LPR = 8; CALL; } break;                                                                 \
+        case 64: { constexpr int LPR = 16; CALL; } break;                                                                \
+        default: { constexpr int LPR = 32; CALL; } break;                                                                \
+    }
 
 extern "C" {
 
 int qrec_gate_fwd(const float *d_X, const float *d_W, const float *d_bias, int64_t n_rows, int32_t ld, float *d_Y, float *d_S,
                   void *stream) {
     QREC_REQUIRE(d_X && d_W && d_bias && d_Y && d_S && n_rows >= 0, "qrec_gate_fwd: bad argument");
+    QREC_REQUIRE(ld == 32 || ld == 64 || ld == 128, "qrec_gate_fwd: row stride must be 32, 64 or 128 floats: the weight matrix is staged in LDS (got %d)", ld);
     if (n_rows == 0) return QREC_OK;
     hipStream_t st = as_stream(stream);
-    const size_t lds = (size_t)ld * ld * sizeof(float);
-    QREC_MHCN_LD_SWITCH("qrec_gate_fwd", {
-        if (lds > 64 * 1024) QREC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gate_fwd_kernel<LPR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const size_t lds = (size_t)ld * ld * sizeof(float);         // at most 64 KiB: within the default dynamic-LDS limit
+    QREC_MHCN_GATE_LD_SWITCH({
         int blocks = launch_rows<LPR>(n_rows); if (blocks > 512) blocks = 512;
         hipLaunchKernelGGL((gate_fwd_kernel<LPR>), dim3((unsigned)blocks), dim3(256), lds, st, d_X, d_W, d_bias, n_rows, d_Y, d_S);
     })
@@ -409,11 +418,11 @@ int qrec_gate_fwd(const float *d_X, const float *d_W, const float *d_bias, int64
 int qrec_gate_bwd(const float *d_X, const float *d_S, const float *d_dY, const float *d_W, int64_t n_rows, int32_t d, int32_t ld,
                   float dy_scale, float *d_Q, float *d_dX, int32_t accumulate, void *stream) {
     QREC_REQUIRE(d_X && d_S && d_dY && d_W && d_Q && d_dX && n_rows >= 0 && d >= 1 && d <= ld, "qrec_gate_bwd: bad argument");
+    QREC_REQUIRE(ld == 32 || ld == 64 || ld == 128, "qrec_gate_bwd: row stride must be 32, 64 or 128 floats: the weight matrix is staged in LDS (got %d)", ld);
     if (n_rows == 0) return QREC_OK;
     hipStream_t st = as_stream(stream);
     const size_t lds = (size_t)ld * ld * sizeof(float);
-    QREC_MHCN_LD_SWITCH("qrec_gate_bwd", {
-        if (lds > 64 * 1024) QREC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gate_bwd_kernel<LPR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    QREC_MHCN_GATE_LD_SWITCH({
         int blocks = launch_rows<LPR>(n_rows); if (blocks > 512) blocks = 512;
         hipLaunchKernelGGL((gate_bwd_kernel<LPR>), dim3((unsigned)blocks), dim3(256), lds, st, d_X, d_S, d_dY, d_W, d, n_rows, dy_scale, d_Q, d_dX, accumulate);
     })

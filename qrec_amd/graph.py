@@ -1845,6 +1845,8 @@ class MHCNTrainer:
 
     def __init__(self, U0, V0, weights, H, R, n_layers: int, lr: float, reg: float, ss_rate: float, loss_eps: float = 1e-7,
                  seed: int = 0):
+        if U0.shape[1] > 128:
+            raise ValueError("MHCN on the device supports num.factors up to 128 (the gates keep their d x d weight matrix in LDS)")
         self.ows = _ordered_ws()
         self.nu, self.ni, self.d = U0.shape[0], V0.shape[0], U0.shape[1]
         self.n = self.nu + self.ni

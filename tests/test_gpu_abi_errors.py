@@ -101,6 +101,8 @@ def test_social_and_graph_model_entry_points_refuse_bad_arguments_and_accept_emp
     _err(lambda: capi.gate_fwd(T, None, f32(64), 60, 64, S, S))
     _err(lambda: capi.gate_fwd(T, f32(48, 48), f32(48), 60, 48, S, S))
     _err(lambda: capi.gate_bwd(T, T, T, f32(64, 64), 60, 65, 64, S, S, False))                          # d > ld
+    assert "128" in _err(lambda: capi.gate_fwd(T, f32(256, 256), f32(256), 15, 256, S, S))              # ld x ld floats do not fit in LDS
+    assert "128" in _err(lambda: capi.gate_bwd(T, T, T, f32(256, 256), 15, 200, 256, S, S, False))
     _err(lambda: capi.hss_loss_grad(T, T, 60, 70, 64, [idx] * 10, 1.0, ws, S, S, out))                 # d > ld
     _err(lambda: capi.random_permutations(1 << 20, 1 << 12, 0, 0, ws, idx))                            # n * count >= 2^31
     _err(lambda: capi.small_permutations(5000, 1, 0, 0, idx, idx))                                     # n > 4096
