@@ -1,7 +1,7 @@
 // Order-exact BPR beyond one wavefront: the static schedule of exact_schedule.cpp executed by ONE workgroup.
 //
 // model/ranking/BPR.py:45-53 applied strictly in the reference's order is a dependence DAG ~n/6 deep (every user run is a
-// chain through P[u], popular items link the runs).  The walker of bpr_sgd.hip (one wavefront, one triplet after the
+// chain through P[u], popular items link the runs).  The walker of sgd_walkers.hip (one wavefront, one triplet after the
 // other, ~1 us each) leaves the DAG's width unused.  Here a workgroup of NW wavefronts advances one SCHEDULE STEP per
 // barrier: wavefront w applies the step's w-th triplet -- all triplets of a step are independent, every dependence points
 // at least one step back.  What bounds a step is the latency of one triplet's dependent chain, so everything else is
@@ -21,20 +21,11 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "common.h"
+#include "lane_row.h"
 
 using namespace qrec;
 
 namespace {
-
-template <typename T> __device__ inline T dev_exp(T x);
-template <> __device__ inline float dev_exp<float>(float x) { return expf(x); }
-template <> __device__ inline double dev_exp<double>(double x) { return exp(x); }
-
-__device__ inline double neg_log_sigmoid_d(double x) { return x >= 0.0 ? log1p(exp(-x)) : (-x + log1p(exp(x))); }
-
-template <typename T>
-__device__ inline T wave_allreduce_sum(T v) { return wave_sum_dpp(v); }   // common.h: DPP, not the LDS crossbar
 
 struct Entry {      // as loaded: nothing is computed from a/b before the step that uses them (a use is a wait)
     int4 a, b;      // {u, i, j, t}, {src_P, src_Qi, src_Qj, -}
@@ -134,7 +125,7 @@ __global__ __launch_bounds__((sizeof(T) * EPL >= 32) ? 512 : 1024) void bpr_leve
             T di = 0, dj = 0;
 #pragma unroll
             for (int e = 0; e < EPL; e++) { di += row[0][e] * row[1][e]; dj += row[0][e] * row[2][e]; }
-            di = wave_allreduce_sum(di); dj = wave_allreduce_sum(dj);
+            di = wave_sum_dpp(di); dj = wave_sum_dpp(dj);
             x = di - dj;
             const T sg = T(1) / (T(1) + dev_exp<T>(-x));
             const T g = lr * (T(1) - sg);
@@ -393,7 +384,7 @@ __global__ __launch_bounds__(256) void expand_schedule_kernel(const int4 *__rest
 }
 
 // sum over the epoch's triplets of -log(sigmoid(x)): model/ranking/BPR.py:53 from the logged x.  fp64 tables: the
-// reference's own expression -log(1/(1+exp(-x))); fp32: the stable form (bpr_sgd.hip).  Block partials are added in
+// reference's own expression -log(1/(1+exp(-x))); fp32: the stable form (lane_row.h).  Block partials are added in
 // block order by the last block: a deterministic sum.
 template <typename T>
 __global__ __launch_bounds__(256) void nll_sum_kernel(const T *__restrict__ xlog, int64_t n, double *__restrict__ partial,
@@ -402,7 +393,7 @@ __global__ __launch_bounds__(256) void nll_sum_kernel(const T *__restrict__ xlog
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
         const double x = (double)xlog[t];
         if constexpr (sizeof(T) == 8) acc += -log(1.0 / (1.0 + exp(-x)));
-        else acc += neg_log_sigmoid_d(x);
+        else acc += neg_log_sigmoid(x);
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, kWave);
@@ -496,7 +487,7 @@ extern "C" {
 
 int qrec_bpr_exact_width(int dtype, int32_t d, int32_t *width) {
     QREC_REQUIRE(width && d >= 1 && d <= 256 && (dtype == QREC_F32 || dtype == QREC_F64), "qrec_bpr_exact_width: bad arguments");
-    const int epl = d <= 64 ? 1 : d <= 128 ? 2 : 4;
+    const int epl = lane_row_epl(d);
     const size_t per_wave = (size_t)3 * 3 * 64 * epl * (dtype == QREC_F64 ? 8 : 4);
     int nw = (int)((size_t)144 * 1024 / per_wave);              // of the CU's 160 KiB
     if (nw > QREC_EXACT_MAX_WIDTH) nw = QREC_EXACT_MAX_WIDTH;
@@ -508,19 +499,16 @@ int qrec_bpr_sgd_scheduled(void *d_P, void *d_Q, int dtype, int32_t d, int32_t l
                            const int32_t *d_step_off, int64_t n_steps, int32_t width, int64_t n, double lr, double regU,
                            double regI, void *d_xlog, double *d_scratch, double *d_loss, void *stream) {
     QREC_REQUIRE(d_P && d_Q && d_loss && n >= 0 && n_steps >= 0 && n_steps < (1ll << 31), "qrec_bpr_sgd_scheduled: bad arguments");
-    QREC_REQUIRE(d >= 1 && d <= 256 && ld >= d, "qrec_bpr_sgd_scheduled: need 1 <= d <= 256, ld >= d (got d=%d ld=%d)", d, ld);
-    QREC_REQUIRE(dtype == QREC_F32 || dtype == QREC_F64, "qrec_bpr_sgd_scheduled: bad dtype %d", dtype);
+    if (int rc = check_lane_row("qrec_bpr_sgd_scheduled", dtype, d, ld)) return rc;
     hipStream_t st = as_stream(stream);
     if (n == 0) { QREC_HIP_CHECK(hipMemsetAsync(d_loss, 0, sizeof(double), st)); return QREC_OK; }
     QREC_REQUIRE(d_entries && d_step_off && d_xlog && d_scratch, "qrec_bpr_sgd_scheduled: null schedule / scratch");
     int32_t max_w = 0;
     qrec_bpr_exact_width(dtype, d, &max_w);
     QREC_REQUIRE(width >= 1 && width <= max_w, "qrec_bpr_sgd_scheduled: width %d outside 1..%d for this table", width, max_w);
-    int rc;
-#define QREC_LV(T, EPL) rc = launch_levels<T, EPL>(d_P, d_Q, d, ld, d_entries, d_step_off, (int)n_steps, width, lr, regU, regI, d_xlog, n, st)
-    if (dtype == QREC_F64) { if (d <= 64) QREC_LV(double, 1); else if (d <= 128) QREC_LV(double, 2); else QREC_LV(double, 4); }
-    else { if (d <= 64) QREC_LV(float, 1); else if (d <= 128) QREC_LV(float, 2); else QREC_LV(float, 4); }
-#undef QREC_LV
+    const int rc = with_row_type(dtype, d, [&](auto t, auto epl) {
+        return launch_levels<decltype(t), epl()>(d_P, d_Q, d, ld, d_entries, d_step_off, (int)n_steps, width, lr, regU, regI, d_xlog, n, st);
+    });
     if (rc != QREC_OK) return rc;
     // d_scratch: kNllBlocks partials + the ticket word (zero before the first use; the kernel re-arms it)
     unsigned int *ticket = reinterpret_cast<unsigned int *>(d_scratch + kNllBlocks);

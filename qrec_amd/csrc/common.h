@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/qrec_hip.h"
 
@@ -35,6 +36,10 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
 #define QREC_LAUNCH_CHECK() QREC_HIP_CHECK(hipGetLastError())
 
 constexpr int kWave = 64;  // gfx950 wavefront
+
+// a runtime value -> a template argument, stated once per ladder: `with_x(value, [&](auto c) { kernel<c()> ... })`
+// (with_nc of eval_topk.hip, with_epl of lane_row.h)
+template <int V> using int_c = std::integral_constant<int, V>;
 
 // ---- workspaces: a file states each layout ONCE, as a function (Carver &, shape...) that returns or fills the file's Ws
 // struct.  layout_bytes runs it on a null base for the *_bytes entry point, carve on the caller's buffer; an entry point that

@@ -1722,7 +1722,6 @@ FusedWs fused_layout(Carver &c, const FusedGeom &g, int n_items, int ld) {
 
 // ld -> the template arguments of the fused route's kernels, stated once.  fp32 scoring and the selection: NC column chunks of 64.
 // bf16 kernels: NM MFMA steps of 16 columns and NU user tiles per wavefront (FusedGeom::nu: 4, or 2 at ld = 128 and under QREC_EVAL_NU=2).
-template <int V> using int_c = std::integral_constant<int, V>;
 template <typename F> void with_nc(int ld, F f) { if (ld <= 64) f(int_c<1>{}); else f(int_c<2>{}); }
 template <typename F> void with_nm_nu(int ld, int nu, F f) {
     if (ld == 32) f(int_c<2>{}, int_c<4>{});

@@ -1,7 +1,7 @@
 // Social-trust rating models (model/rating/{SoRec,SoReg,SocialMF,RSTE,SREE,LOCABAL,SocialFD}.py), fp64, order-exact.
 // LOCABAL and SocialFD, whose passes carry a dense d x d matrix, have their own section further down.
 //
-// The rating passes of SoRec / SoReg (PMF), SREE (EE) and SocialMF (PMF on copies) are mf_ordered_kernel of bpr_sgd.hip.
+// The rating passes of SoRec / SoReg (PMF), SREE (EE) and SocialMF (PMF on copies) are mf_ordered_kernel of sgd_walkers.hip.
 // Here are the rest:
 //   * rste_ordered_kernel: RSTE's rating pass (RSTE.py:22-40,42-62), whose prediction blends P[u].Q[i] with the
 //     followees' P[f].Q[i] -- one wavefront, lane = column, like mf_ordered_kernel;
@@ -17,26 +17,11 @@
 // launch.  A step's arithmetic is the reference's sequential arithmetic, followees walked in dict order, so a schedule of
 // width 1 (one step per level) is the plain sequential walk and every schedule gives the same bits.  Each step writes its
 // loss term(s) to slots indexed by their position in the reference order; loss_fold_kernel adds them one after the other.
-#include "common.h"
+#include "lane_row.h"
 
 using namespace qrec;
 
 namespace {
-
-__device__ inline double wsum(double v) { return wave_sum_dpp(v); }
-
-template <int EPL>
-__device__ inline void load_row(double (&x)[EPL], const double *row, int lane, int d) {
-#pragma unroll
-    for (int e = 0; e < EPL; e++) x[e] = (lane + 64 * e) < d ? row[lane + 64 * e] : 0.0;
-}
-
-template <int EPL>
-__device__ inline void store_row(double *row, const double (&x)[EPL], int lane, int d) {
-#pragma unroll
-    for (int e = 0; e < EPL; e++)
-        if ((lane + 64 * e) < d) row[lane + 64 * e] = x[e];
-}
 
 // RSTE.py:26-37 with predictForRating :42-62.  den[u] = the followees' weight sum as numpy's weights.sum() gives it (host);
 // den != 0: pred = alpha*P[u].Q[i] + ((1-alpha)*sum_f w_f (P[f].Q[i])) / den, else pred = P[u].Q[i].  p, q are views.
@@ -48,29 +33,21 @@ __global__ __launch_bounds__(64) void rste_ordered_kernel(double *__restrict__ P
                                                           const double *__restrict__ rating, int64_t n, double lr, double alpha,
                                                           double regU, double regI, double *__restrict__ loss_out) {
 #pragma clang fp contract(off)
-    const int lane = threadIdx.x;
+    const LaneRow<double, EPL> R(threadIdx.x, d, ld);
     double loss = 0.0;
     for (int64_t t = 0; t < n; t++) {
         const int u = u_idx[t], i = i_idx[t];
-        double *p = P + (int64_t)u * ld;
-        double *q = Q + (int64_t)i * ld;
-        double pv[EPL], qv[EPL];
-        load_row(pv, p, lane, d);
-        load_row(qv, q, lane, d);
-        double dot = 0.0;
-#pragma unroll
-        for (int e = 0; e < EPL; e++) dot += pv[e] * qv[e];
-        dot = wsum(dot);
+        double pv[EPL], qv[EPL], fv[EPL];
+        R.load(pv, P, u);
+        R.load(qv, Q, i);
+        const double dot = row_dot(pv, qv);
         const double den = den_u[u];
         double pred = dot;
         if (den != 0.0) {
             double fpred = 0.0;
             for (int64_t k = fe_ptr[u]; k < fe_ptr[u + 1]; k++) {
-                const double *f = P + (int64_t)fe_ids[k] * ld;
-                double s = 0.0;
-#pragma unroll
-                for (int e = 0; e < EPL; e++) s += ((lane + 64 * e) < d ? f[lane + 64 * e] : 0.0) * qv[e];
-                fpred += fe_w[k] * wsum(s);
+                R.load(fv, P, fe_ids[k]);
+                fpred += fe_w[k] * row_dot(fv, qv);
             }
             pred = alpha * dot + ((1.0 - alpha) * fpred) / den;
         }
@@ -82,10 +59,10 @@ __global__ __launch_bounds__(64) void rste_ordered_kernel(double *__restrict__ P
             pv[e] += lr * (ae * qv[e] - regU * pv[e]);
             qv[e] += lr * (ae * pv[e] - regI * qv[e]);
         }
-        store_row(p, pv, lane, d);
-        store_row(q, qv, lane, d);
+        R.store(P, u, pv);
+        R.store(Q, i, qv);
     }
-    if (lane == 0) *loss_out = loss;
+    if (R.lane == 0) *loss_out = loss;
 }
 
 // One user's step of the per-user pass; MODE 0 = SocialMF, 1 = SoReg, 2 = SREE (QREC_SOCIAL_* of qrec_hip.h).
@@ -102,10 +79,10 @@ __device__ inline void user_step(double *__restrict__ P, int d, int ld, int lane
                                  const int64_t *__restrict__ fr_ptr, const int32_t *__restrict__ fr_ids, const double *__restrict__ fr_w,
                                  double lr, double coef, double *__restrict__ slots) {
 #pragma clang fp contract(off)
+    const LaneRow<double, EPL> R(lane, d, ld);
     const int u = step_user[k];
-    double *prow = P + (int64_t)u * ld;
     double p[EPL];
-    load_row(p, prow, lane, d);
+    R.load(p, P, u);
     const int64_t b = fe_ptr[k], en = fe_ptr[k + 1];
     if constexpr (MODE == 0) {
         double fp[EPL], denom = 0.0;
@@ -119,7 +96,7 @@ __device__ inline void user_step(double *__restrict__ P, int d, int ld, int lane
 #pragma unroll
                 for (int e = 0; e < EPL; e++) x[e] = p[e];
             } else {
-                load_row(x, P + (int64_t)f * ld, lane, d);
+                R.load(x, P, f);
             }
 #pragma unroll
             for (int e = 0; e < EPL; e++) fp[e] += w * x[e];
@@ -131,7 +108,7 @@ __device__ inline void user_step(double *__restrict__ P, int d, int ld, int lane
             rl[e] = denom != 0.0 ? p[e] - fp[e] / denom : 0.0;
             dd += rl[e] * rl[e];
         }
-        dd = wsum(dd);
+        dd = wave_sum_dpp(dd);
         if (lane == 0) slots[k] = coef * dd;
         const double c = lr * coef;
 #pragma unroll
@@ -148,7 +125,7 @@ __device__ inline void user_step(double *__restrict__ P, int d, int ld, int lane
 #pragma unroll
                 for (int e = 0; e < EPL; e++) x[e] = p[e];
             } else {
-                load_row(x, P + (int64_t)f * ld, lane, d);
+                R.load(x, P, f);
             }
 #pragma unroll
             for (int e = 0; e < EPL; e++) {
@@ -156,7 +133,7 @@ __device__ inline void user_step(double *__restrict__ P, int d, int ld, int lane
                 f1[e] += s * df;
                 dd += df * df;
             }
-            simsum += s * wsum(dd);
+            simsum += s * wave_sum_dpp(dd);
             if (lane == 0) slots[j] = simsum;
         }
         for (int64_t j = fr_ptr[k]; j < fr_ptr[k + 1]; j++) {
@@ -167,7 +144,7 @@ __device__ inline void user_step(double *__restrict__ P, int d, int ld, int lane
 #pragma unroll
                 for (int e = 0; e < EPL; e++) x[e] = p[e];
             } else {
-                load_row(x, P + (int64_t)g * ld, lane, d);
+                R.load(x, P, g);
             }
 #pragma unroll
             for (int e = 0; e < EPL; e++) f2[e] += s * (p[e] - x[e]);
@@ -186,7 +163,7 @@ __device__ inline void user_step(double *__restrict__ P, int d, int ld, int lane
 #pragma unroll
                 for (int e = 0; e < EPL; e++) z[e] = p[e];
             } else {
-                load_row(z, P + (int64_t)v * ld, lane, d);
+                R.load(z, P, v);
             }
             const double c = la * w;
 #pragma unroll
@@ -196,11 +173,11 @@ __device__ inline void user_step(double *__restrict__ P, int d, int ld, int lane
                 const double df = p[e] - (self ? p[e] : z[e]);
                 dd += df * df;
             }
-            dd = wsum(dd);
+            dd = wave_sum_dpp(dd);
             if (lane == 0) slots[j] = (coef * w) * dd;
         }
     }
-    store_row(prow, p, lane, d);
+    R.store(P, u, p);
 }
 
 template <int EPL, int MODE>
@@ -228,28 +205,25 @@ __global__ __launch_bounds__(1024) void sorec_levels_kernel(double *__restrict__
                                                             int n_levels, double lr, double regS, double regZ,
                                                             double *__restrict__ slots) {
 #pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const LaneRow<double, EPL> R(threadIdx.x & 63, d, ld);
     for (int L = 0; L < n_levels; L++) {
         const int end = level_ptr[L + 1];
         for (int s = level_ptr[L] + w; s < end; s += nw) {
-            const int k = order[s];
-            double *prow = P + (int64_t)rel_u[k] * ld;
-            double *zrow = Z + (int64_t)rel_v[k] * ld;
-            double p[EPL], z[EPL], dot = 0.0;
-            load_row(p, prow, lane, d);
-            load_row(z, zrow, lane, d);
-#pragma unroll
-            for (int e = 0; e < EPL; e++) dot += p[e] * z[e];
-            const double euv = rel_w[k] * rel_t[k] - wsum(dot);
-            if (lane == 0) slots[k] = regS * (euv * euv);
+            const int k = order[s], u = rel_u[k], v = rel_v[k];
+            double p[EPL], z[EPL];
+            R.load(p, P, u);
+            R.load(z, Z, v);
+            const double euv = rel_w[k] * rel_t[k] - row_dot(p, z);
+            if (R.lane == 0) slots[k] = regS * (euv * euv);
             const double c = regS * euv;
 #pragma unroll
             for (int e = 0; e < EPL; e++) {
                 p[e] += lr * (c * z[e]);
                 z[e] += lr * (c * p[e] - regZ * z[e]);
             }
-            store_row(prow, p, lane, d);
-            store_row(zrow, z, lane, d);
+            R.store(P, u, p);
+            R.store(Z, v, z);
         }
         __syncthreads();
     }
@@ -262,21 +236,6 @@ __global__ __launch_bounds__(64) void loss_fold_kernel(double *__restrict__ runn
     double acc = *running;
     for (int64_t k = 0; k < n; k++) acc += slots[k];
     *running = acc;
-}
-
-template <int EPL>
-int launch_user_levels(int mode, int nw, double *P, int d, int ld, const int32_t *su, const int64_t *fe_ptr, const int32_t *fe_ids,
-                       const double *fe_w, const int64_t *fr_ptr, const int32_t *fr_ids, const double *fr_w, const int32_t *order,
-                       const int32_t *level_ptr, int n_levels, double lr, double coef, double *slots, hipStream_t st) {
-#define QREC_USER_LAUNCH(M)                                                                                                     \
-    hipLaunchKernelGGL((social_user_levels_kernel<EPL, M>), dim3(1), dim3(64 * nw), 0, st, P, d, ld, su, fe_ptr, fe_ids, fe_w, \
-                       fr_ptr, fr_ids, fr_w, order, level_ptr, n_levels, lr, coef, slots)
-    if (mode == QREC_SOCIAL_SOCIALMF) QREC_USER_LAUNCH(0);
-    else if (mode == QREC_SOCIAL_SOREG) QREC_USER_LAUNCH(1);
-    else QREC_USER_LAUNCH(2);
-#undef QREC_USER_LAUNCH
-    QREC_LAUNCH_CHECK();
-    return QREC_OK;
 }
 
 // ---- LOCABAL and SocialFD: passes that carry a dense d x d matrix H ---------------------------------------------------------
@@ -415,19 +374,14 @@ __global__ __launch_bounds__(64) void locabal_ordered_kernel(double *__restrict_
                                                              int64_t n, double lr, double regU, double regI,
                                                              double *__restrict__ loss_out) {
 #pragma clang fp contract(off)
-    const int lane = threadIdx.x;
+    const LaneRow<double, EPL> R(threadIdx.x, d, ld);
     double loss = 0.0;
     for (int64_t t = 0; t < n; t++) {
         const int u = u_idx[t], i = i_idx[t];
-        double *prow = P + (int64_t)u * ld;
-        double *qrow = Q + (int64_t)i * ld;
         double p[EPL], q[EPL], pn[EPL], qn[EPL];
-        load_row(p, prow, lane, d);
-        load_row(q, qrow, lane, d);
-        double dot = 0.0;
-#pragma unroll
-        for (int e = 0; e < EPL; e++) dot += p[e] * q[e];
-        const double err = rating[t] - wsum(dot);
+        R.load(p, P, u);
+        R.load(q, Q, i);
+        const double err = rating[t] - row_dot(p, q);
         const double w = w_user[u];
         loss += w != 0.0 ? w * (err * err) : err * err;
 #pragma unroll
@@ -445,10 +399,10 @@ __global__ __launch_bounds__(64) void locabal_ordered_kernel(double *__restrict_
             pn[e] += lr * (err * q[e] - regU * p[e]);
             qn[e] += lr * (err * p[e] - regI * q[e]);
         }
-        store_row(prow, pn, lane, d);
-        store_row(qrow, qn, lane, d);
+        R.store(P, u, pn);
+        R.store(Q, i, qn);
     }
-    if (lane == 0) *loss_out = loss;
+    if (R.lane == 0) *loss_out = loss;
 }
 
 // LOCABAL.py:68-80, edge by edge: p = P[u], q = P[k] (copies); e = sim - (p^T H) . q; slot = alpha*e^2;
@@ -644,18 +598,13 @@ int qrec_rste_sgd_ordered(double *d_P, double *d_Q, int32_t d, int32_t ld, const
                           void *stream) {
     QREC_REQUIRE(d_P && d_Q && d_loss && n >= 0, "qrec_rste_sgd_ordered: null argument");
     QREC_REQUIRE(n == 0 || (d_u && d_i && d_rating && d_fe_indptr && d_fe_den), "qrec_rste_sgd_ordered: null index array");
-    QREC_REQUIRE(d >= 1 && d <= 256 && ld >= d, "qrec_rste_sgd_ordered: need 1 <= d <= 256, ld >= d (got d=%d ld=%d)", d, ld);
+    if (int rc = check_lane_row("qrec_rste_sgd_ordered", QREC_F64, d, ld)) return rc;
     hipStream_t st = as_stream(stream);
     if (n == 0) { QREC_HIP_CHECK(hipMemsetAsync(d_loss, 0, sizeof(double), st)); return QREC_OK; }
-#define QREC_RSTE_LAUNCH(EPL)                                                                                                  \
-    hipLaunchKernelGGL((rste_ordered_kernel<EPL>), dim3(1), dim3(64), 0, st, d_P, d_Q, d, ld, d_fe_indptr, d_fe_ids, d_fe_w,   \
-                       d_fe_den, d_u, d_i, d_rating, n, lr, alpha, regU, regI, d_loss)
-    if (d <= 64) QREC_RSTE_LAUNCH(1);
-    else if (d <= 128) QREC_RSTE_LAUNCH(2);
-    else QREC_RSTE_LAUNCH(4);
-#undef QREC_RSTE_LAUNCH
-    QREC_LAUNCH_CHECK();
-    return QREC_OK;
+    return with_epl(d, [&](auto epl) {
+        return launch_waves(rste_ordered_kernel<epl()>, 1, st, d_P, d_Q, d, ld, d_fe_indptr, d_fe_ids, d_fe_w, d_fe_den, d_u, d_i, d_rating, n,
+                            lr, alpha, regU, regI, d_loss);
+    });
 }
 
 int qrec_social_user_pass(int mode, double *d_P, int32_t d, int32_t ld, const int32_t *d_step_user, int64_t n_steps,
@@ -668,17 +617,17 @@ int qrec_social_user_pass(int mode, double *d_P, int32_t d, int32_t ld, const in
     QREC_REQUIRE(n_steps == 0 || (d_step_user && d_fe_indptr && d_order && d_level_ptr && d_slots),
                  "qrec_social_user_pass: null step array");
     QREC_REQUIRE(mode != QREC_SOCIAL_SOREG || n_steps == 0 || d_fr_indptr, "qrec_social_user_pass: SoReg needs the follower CSR");
-    QREC_REQUIRE(d >= 1 && d <= 256 && ld >= d, "qrec_social_user_pass: need 1 <= d <= 256, ld >= d (got d=%d ld=%d)", d, ld);
+    if (int rc = check_lane_row("qrec_social_user_pass", QREC_F64, d, ld)) return rc;
     QREC_REQUIRE(n_waves >= 1 && n_waves <= QREC_SOCIAL_MAX_WAVES, "qrec_social_user_pass: need 1 <= n_waves <= %d, got %d",
                  QREC_SOCIAL_MAX_WAVES, n_waves);
     if (n_steps == 0 || n_levels == 0) return QREC_OK;
-    hipStream_t st = as_stream(stream);
-    if (d <= 64) return launch_user_levels<1>(mode, n_waves, d_P, d, ld, d_step_user, d_fe_indptr, d_fe_ids, d_fe_w, d_fr_indptr, d_fr_ids,
-                                              d_fr_w, d_order, d_level_ptr, n_levels, lr, coef, d_slots, st);
-    if (d <= 128) return launch_user_levels<2>(mode, n_waves, d_P, d, ld, d_step_user, d_fe_indptr, d_fe_ids, d_fe_w, d_fr_indptr, d_fr_ids,
-                                               d_fr_w, d_order, d_level_ptr, n_levels, lr, coef, d_slots, st);
-    return launch_user_levels<4>(mode, n_waves, d_P, d, ld, d_step_user, d_fe_indptr, d_fe_ids, d_fe_w, d_fr_indptr, d_fr_ids, d_fr_w,
-                                 d_order, d_level_ptr, n_levels, lr, coef, d_slots, st);
+    return with_epl(d, [&](auto epl) {
+        auto launch = [&](auto m) {
+            return launch_waves(social_user_levels_kernel<epl(), m()>, n_waves, as_stream(stream), d_P, d, ld, d_step_user, d_fe_indptr, d_fe_ids,
+                                d_fe_w, d_fr_indptr, d_fr_ids, d_fr_w, d_order, d_level_ptr, n_levels, lr, coef, d_slots);
+        };
+        return mode == QREC_SOCIAL_SOCIALMF ? launch(int_c<0>{}) : mode == QREC_SOCIAL_SOREG ? launch(int_c<1>{}) : launch(int_c<2>{});
+    });
 }
 
 int qrec_sorec_relation_pass(double *d_P, double *d_Z, int32_t d, int32_t ld, const int32_t *d_rel_u, const int32_t *d_rel_v,
@@ -688,20 +637,14 @@ int qrec_sorec_relation_pass(double *d_P, double *d_Z, int32_t d, int32_t ld, co
     QREC_REQUIRE(d_P && d_Z && n_rel >= 0 && n_rel < (int64_t)1 << 31 && n_levels >= 0, "qrec_sorec_relation_pass: null argument");
     QREC_REQUIRE(n_rel == 0 || (d_rel_u && d_rel_v && d_rel_t && d_rel_w && d_order && d_level_ptr && d_slots),
                  "qrec_sorec_relation_pass: null relation array");
-    QREC_REQUIRE(d >= 1 && d <= 256 && ld >= d, "qrec_sorec_relation_pass: need 1 <= d <= 256, ld >= d (got d=%d ld=%d)", d, ld);
+    if (int rc = check_lane_row("qrec_sorec_relation_pass", QREC_F64, d, ld)) return rc;
     QREC_REQUIRE(n_waves >= 1 && n_waves <= QREC_SOCIAL_MAX_WAVES, "qrec_sorec_relation_pass: need 1 <= n_waves <= %d, got %d",
                  QREC_SOCIAL_MAX_WAVES, n_waves);
     if (n_rel == 0 || n_levels == 0) return QREC_OK;
-    hipStream_t st = as_stream(stream);
-#define QREC_SOREC_LAUNCH(EPL)                                                                                                   \
-    hipLaunchKernelGGL((sorec_levels_kernel<EPL>), dim3(1), dim3(64 * n_waves), 0, st, d_P, d_Z, d, ld, d_rel_u, d_rel_v, d_rel_t, \
-                       d_rel_w, d_order, d_level_ptr, n_levels, lr, regS, regZ, d_slots)
-    if (d <= 64) QREC_SOREC_LAUNCH(1);
-    else if (d <= 128) QREC_SOREC_LAUNCH(2);
-    else QREC_SOREC_LAUNCH(4);
-#undef QREC_SOREC_LAUNCH
-    QREC_LAUNCH_CHECK();
-    return QREC_OK;
+    return with_epl(d, [&](auto epl) {
+        return launch_waves(sorec_levels_kernel<epl()>, n_waves, as_stream(stream), d_P, d_Z, d, ld, d_rel_u, d_rel_v, d_rel_t, d_rel_w, d_order,
+                            d_level_ptr, n_levels, lr, regS, regZ, d_slots);
+    });
 }
 
 int qrec_loss_fold(double *d_running, const double *d_slots, int64_t n, void *stream) {
@@ -738,14 +681,9 @@ int qrec_locabal_sgd_ordered(double *d_P, double *d_Q, int32_t d, int32_t ld, co
     QREC_H_WIDTH("qrec_locabal_sgd_ordered");
     hipStream_t st = as_stream(stream);
     if (n == 0) { QREC_HIP_CHECK(hipMemsetAsync(d_loss, 0, sizeof(double), st)); return QREC_OK; }
-    if (d <= 64)
-        hipLaunchKernelGGL((locabal_ordered_kernel<1>), dim3(1), dim3(64), 0, st, d_P, d_Q, d, ld, d_w_user, d_u, d_i, d_rating, n, lr,
-                           regU, regI, d_loss);
-    else
-        hipLaunchKernelGGL((locabal_ordered_kernel<2>), dim3(1), dim3(64), 0, st, d_P, d_Q, d, ld, d_w_user, d_u, d_i, d_rating, n, lr,
-                           regU, regI, d_loss);
-    QREC_LAUNCH_CHECK();
-    return QREC_OK;
+    return with_epl<2>(d, [&](auto epl) {       // QREC_H_WIDTH has refused d > 128
+        return launch_waves(locabal_ordered_kernel<epl()>, 1, st, d_P, d_Q, d, ld, d_w_user, d_u, d_i, d_rating, n, lr, regU, regI, d_loss);
+    });
 }
 
 int qrec_locabal_social_pass(double *d_P, double *d_H, int32_t d, int32_t ld, const int32_t *d_edge_u, const int32_t *d_edge_k,

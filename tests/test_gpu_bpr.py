@@ -180,7 +180,7 @@ def test_basicmf_model_end_to_end_reproduces_reference_run():
 
 
 @pytest.mark.parametrize("variant", [capi.MF_BASIC, capi.MF_PMF, capi.MF_SVD, capi.MF_EE])
-@pytest.mark.parametrize("dim,dtype", [(10, np.float64), (64, np.float64), (200, np.float64), (50, np.float32)])
+@pytest.mark.parametrize("dim,dtype", [(10, np.float64), (64, np.float64), (200, np.float64), (50, np.float32), (65, np.float32), (129, np.float32)])
 def test_mf_family_kernel_matches_oracle(variant, dim, dtype):
     """BasicMF / PMF / SVD recurrences (model/rating/{BasicMF,PMF,SVD}.py) on synthetic ratings."""
     rng = np.random.default_rng(100 + dim + variant)
@@ -1125,22 +1125,23 @@ def test_svdpp_kernel_and_model_reproduce_the_reference_run():
     from qrec_amd.engine import SvdppSgd
     from qrec_amd.model.rating.SVDPlusPlus import SVDPlusPlus
     rng = np.random.default_rng(55)
-    U, I, n, dim = 200, 300, 6000, 12
+    U, I, n = 200, 300, 6000
     u = rng.integers(0, U, n, dtype=np.int32); i = rng.integers(0, I, n, dtype=np.int32)
     r = rng.integers(1, 11, n).astype(np.float64) / 2
     rated = user_item_csr(u, i, r, U, I)
-    P0, Q0, Y0 = rng.random((U, dim)) / 3, rng.random((I, dim)) / 3, rng.random((I, dim)) / 3
-    Bu0, Bi0 = rng.random(U) / 5, rng.random(I) / 5
-    for dtype, tol in ((np.float64, F64_TOL), (np.float32, F32_TOL)):
-        Pr, Qr, Yr, Bur, Bir = P0.copy(), Q0.copy(), Y0.copy(), Bu0.copy(), Bi0.copy()
-        want = O.svdpp_sgd(Pr, Qr, Yr, Bur, Bir, rated.indptr, rated.indices, u, i, r, 0.01, 0.01, 0.02, 0.05, 0.03, float(r.mean()))
-        t = DeviceTables(P0, Q0, dtype)
-        sgd = SvdppSgd(t, Y0, Bu0, Bi0, rated, n)
-        got = sgd.epoch(u, i, r, 0.01, 0.01, 0.02, 0.05, 0.03, float(r.mean()))
-        Pg, Qg = t.download(np.float64); Yg, Bug, Big = sgd.download()
-        check("abs(got - want) / want", abs(got - want) / want, tol)
-        for a, b in ((Pg, Pr), (Qg, Qr), (Yg, Yr), (Bug, Bur), (Big, Bir)):
-            check("rel_err(a, b)", rel_err(a, b), tol)
+    for dim in (12, 65, 129):      # 65 / 129: the first live column of the second / third register of a lane's row
+        P0, Q0, Y0 = rng.random((U, dim)) / 3, rng.random((I, dim)) / 3, rng.random((I, dim)) / 3
+        Bu0, Bi0 = rng.random(U) / 5, rng.random(I) / 5
+        for dtype, tol in ((np.float64, F64_TOL), (np.float32, F32_TOL)):
+            Pr, Qr, Yr, Bur, Bir = P0.copy(), Q0.copy(), Y0.copy(), Bu0.copy(), Bi0.copy()
+            want = O.svdpp_sgd(Pr, Qr, Yr, Bur, Bir, rated.indptr, rated.indices, u, i, r, 0.01, 0.01, 0.02, 0.05, 0.03, float(r.mean()))
+            t = DeviceTables(P0, Q0, dtype)
+            sgd = SvdppSgd(t, Y0, Bu0, Bi0, rated, n)
+            got = sgd.epoch(u, i, r, 0.01, 0.01, 0.02, 0.05, 0.03, float(r.mean()))
+            Pg, Qg = t.download(np.float64); Yg, Bug, Big = sgd.download()
+            check("abs(got - want) / want", abs(got - want) / want, tol)
+            for a, b in ((Pg, Pr), (Qg, Qr), (Yg, Yr), (Bug, Bur), (Big, Bir)):
+                check("rel_err(a, b)", rel_err(a, b), tol)
     meta, z = load_golden("svdpp_filmtrust")
     rows = [[f"u{a}", f"i{b}", float(c)] for (a, b), c in zip(z["order0"].tolist(), z["rating0"].tolist())]
     test = [[f"u{a}" if a >= 0 else f"xu{k}", f"i{b}" if b >= 0 else f"xi{k}", float(c)]
@@ -1202,13 +1203,14 @@ def test_bpr_class_on_two_ranks_keeps_replicas_identical_and_trains_like_one_ran
     assert r3.returncode != 0
 
 
+@pytest.mark.parametrize("dim", [20, 65, 129])      # 65 / 129: the first live column of the second / third register of a lane's row
 @pytest.mark.parametrize("dtype,tol", [(np.float64, F64_TOL), (np.float32, F32_TOL)])
-def test_tbpr_ordered_kernel_matches_oracle_including_aliased_rows(dtype, tol):
+def test_tbpr_ordered_kernel_matches_oracle_including_aliased_rows(dtype, tol, dim):
     """qrec_tbpr_sgd_ordered vs the restated TBPR.optimization loop: chained triplets per user, a == b rows (two
     sequential updates of ONE row), consecutive triplets sharing rows, and the per-user regularisation terms carried as
-    running sums of squares."""
+    running sums of squares.  The index streams are drawn before the tables: they are the same at every width."""
     rng = np.random.default_rng(12)
-    U, I, dim = 120, 90, 20
+    U, I = 120, 90
     u_list, a_list, b_list = [], [], []
     for user in rng.permutation(U)[:100]:
         for _ in range(rng.integers(1, 6)):
@@ -1231,6 +1233,7 @@ def test_tbpr_ordered_kernel_matches_oracle_including_aliased_rows(dtype, tol):
     Pg, Qg = t.download(np.float64)
     check("rel_err(Pg, Pr)", rel_err(Pg, Pr), tol)
     check("rel_err(Qg, Qr)", rel_err(Qg, Qr), tol)
+    assert (t.P.numpy()[:, dim:] == 0).all() and (t.Q.numpy()[:, dim:] == 0).all()  # pad stays zero
     # the regularisation part alone: per-user sums of squares of the evolving tables
     Pc, Qc = P0.copy(), Q0.copy()
     only_nll = sum(O.bpr_sgd(Pc, Qc, u[k:k + 1], a[k:k + 1], b[k:k + 1], 0.05, 0.02, 0.03) for k in range(u.size))
@@ -1296,14 +1299,15 @@ def test_tbpr_model_reproduces_the_reference_run(tmp_path):
     assert np.array_equal(capi.state_from_python(random.getstate()), z["py_state"])
 
 
+@pytest.mark.parametrize("dim", [20, 65, 129])
 @pytest.mark.parametrize("dtype,tol", [(np.float64, F64_TOL), (np.float32, F32_TOL)])
-def test_sbpr_ordered_kernel_matches_oracle_including_aliased_rows(dtype, tol):
+def test_sbpr_ordered_kernel_matches_oracle_including_aliased_rows(dtype, tol, dim):
     """qrec_sbpr_sgd_ordered vs the restated SBPR loop (oracle/npref.py, itself pinned to the reference run): users with and without
     social feedback, j == k rows (the negative repeats the friend-consumed item: one row updated in sequence and decayed twice), users
     without any positive (a bare visit: only the per-user loss terms), the running sums of squares."""
     from oracle import npref
     rng = np.random.default_rng(21)
-    U, I, dim = 90, 70, 20
+    U, I = 90, 70
     rows, ps = [], rng.permutation(U)[:80].tolist()
     for user in ps:
         n = int(rng.integers(0, 6))
@@ -1337,6 +1341,7 @@ def test_sbpr_ordered_kernel_matches_oracle_including_aliased_rows(dtype, tol):
     Pg, Qg = t.download(np.float64)
     check("rel_err(Pg, Pr)", rel_err(Pg, Pr), tol)
     check("rel_err(Qg, Qr)", rel_err(Qg, Qr), tol)
+    assert (t.P.numpy()[:, dim:] == 0).all() and (t.Q.numpy()[:, dim:] == 0).all()  # pad stays zero
 
 
 def test_sbpr_model_reproduces_the_reference_run(tmp_path):

@@ -17,7 +17,7 @@ from qrec_amd.social import Relations, UserSteps, sequential_schedule
 
 pytestmark = pytest.mark.gpu
 
-DIMS = (5, 10, 64, 200)
+DIMS = (5, 10, 64, 65, 200)
 
 
 def steps_of(sp: M.UserPass):

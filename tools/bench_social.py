@@ -1,4 +1,4 @@
-"""SoRec / SoReg / SocialMF / RSTE / SREE timing on the MI355X (engine.SocialSgd, social.hip, mf_ordered_kernel).
+"""SoRec / SoReg / SocialMF / RSTE / SREE timing on the MI355X (engine.SocialSgd, social.hip, mf_ordered_kernel of sgd_walkers.hip).
 
     python tools/bench_social.py [out.json]          # default out: profiles/social_bench.json
 
