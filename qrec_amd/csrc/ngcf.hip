@@ -1,90 +1,24 @@
 // NGCF's dense propagation layers (model/ranking/NGCF.py:27-42) and their backward pass.
 //
 //   side = A E (qrec_spmm_csr)
-//   pre  = (side + E) W1 + (E * side) W2                       dense_fwd_kernel      (f32 MFMA)
+//   pre  = (side + E) W1 + (E * side) W2                       layer_fwd_*<SumProductOps>   (f32 MFMA, mfma_layer.h)
 //   act  = leaky_relu(pre, 0.2); nxt = dropout(act, keep); z = l2_normalize(nxt)
 //                                                              activate_rows_kernel
 //   backward:
 //   dnxt = dE_next + normalize_bwd(dz);  dpre = dnxt * gate     dpre_rows_kernel
 //   dA1 = dpre W1^T, dA2 = dpre W2^T;  dside = dA1 + dA2*E;  dE = dA1 + dA2*side
-//                                                              dense_bwd_kernel      (f32 MFMA)
-//   dW1 = (side+E)^T dpre, dW2 = (E*side)^T dpre               wgrad_kernel + wgrad_reduce_kernel (MFMA)
+//                                                              layer_bwd_*<SumProductOps>   (f32 MFMA)
+//   dW1 = (side+E)^T dpre, dW2 = (E*side)^T dpre               layer_wgrad_*<SumProductOps> + wgrad_sum_kernel (MFMA)
 //   dE += A^T dside (qrec_spmm_csr with addend)
 //
 // Tables are [rows][ld] fp32 with ld in {32, 64, 128}; the d x d weights are stored zero-padded as
 // [ld][ld].  The N x d x d products are the only GEMM-shaped work (2 N d^2 FLOP each, K = d small):
 // one wavefront per 32 rows holds its A fragments in registers and sweeps the output column tiles.
-#include "mfma_rows.h"
+#include "mfma_layer.h"
 
 using namespace qrec;
 
 namespace {
-
-// pre[32 rows][ld] = (side + E) W1 + (E*side) W2      NT = ld/32 output column tiles
-// Persistent blocks: the two weight matrices are staged in LDS once per block (2 x LD*LD floats) and every
-// wavefront walks 32-row tiles.  A operand: the lane's own row, 8 float4 loads per table and 64-column chunk;
-// B operand: ds_read_b32 of W[k][32t + r] (consecutive lanes, consecutive banks).  The first version read every B
-// value from global memory right before its MFMA (the compiler keeps such loads one MFMA ahead): ~400 clocks of
-// load latency per 64-clock MFMA, 51 us for 1.1 GFLOP.
-template <int NT>
-__global__ __launch_bounds__(256) void dense_fwd_kernel(const float *__restrict__ E, const float *__restrict__ side,
-                                                        const float *__restrict__ W1, const float *__restrict__ W2,
-                                                        int64_t n_rows, float *__restrict__ pre) {
-    constexpr int LD = 32 * NT;
-    extern __shared__ float s_w[];                  // [2][LD][LD]
-    for (int k = threadIdx.x; k < LD * LD / 4; k += blockDim.x) {
-        reinterpret_cast<f32x4 *>(s_w)[k] = reinterpret_cast<const f32x4 *>(W1)[k];
-        reinterpret_cast<f32x4 *>(s_w + LD * LD)[k] = reinterpret_cast<const f32x4 *>(W2)[k];
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    const int64_t n_tiles = (n_rows + 31) / 32;
-    for (int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * 4) {
-        const int64_t row0 = tile * 32, row = row0 + r;
-        const int64_t rowc = row < n_rows ? row : n_rows - 1;      // rows past the end are computed on a copy, not stored
-        f32x16 acc[NT];
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) acc[t][q] = 0.f;
-        // ld = 128 (NT = 4) has two 64-column chunks: kept a LOOP there -- unrolled, both chunks' 2 x 32 A values are live next to the
-        // 64 accumulator registers and the kernel spilled 126 VGPRs (508 B of scratch per lane)
-#pragma unroll 1
-        for (int c = 0; c < LD; c += 64) {
-            const int k0 = c + 32 * h;
-            const bool kv = k0 < LD;                 // ld = 32: the upper k-slot has no columns and feeds zeros
-            const int kb = kv ? k0 : 0;
-            const float keep = kv ? 1.f : 0.f;
-            const f32x4 *pe = reinterpret_cast<const f32x4 *>(E + rowc * LD + kb);
-            const f32x4 *ps = reinterpret_cast<const f32x4 *>(side + rowc * LD + kb);
-            float a1[32], a2[32];
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const f32x4 e = pe[q], sd = ps[q];
-                a1[4 * q + 0] = (sd.x + e.x) * keep; a2[4 * q + 0] = (e.x * sd.x) * keep;
-                a1[4 * q + 1] = (sd.y + e.y) * keep; a2[4 * q + 1] = (e.y * sd.y) * keep;
-                a1[4 * q + 2] = (sd.z + e.z) * keep; a2[4 * q + 2] = (e.z * sd.z) * keep;
-                a1[4 * q + 3] = (sd.w + e.w) * keep; a2[4 * q + 3] = (e.w * sd.w) * keep;
-            }
-#pragma unroll
-            for (int t = 0; t < NT; t++) {
-                const float *w1 = s_w + kb * LD + 32 * t + r, *w2 = w1 + LD * LD;
-#pragma unroll
-                for (int s = 0; s < 32; s++) {
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], w1[s * LD], acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[s], w2[s * LD], acc[t], 0, 0, 0);
-                }
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) {
-                const int64_t orow = row0 + cd_row(q, h);
-                if (orow < n_rows) pre[orow * LD + 32 * t + r] = acc[t][q];
-            }
-    }
-}
 
 // One group of LPR lanes per row (float4 per lane).  In place on `pre_gate`: reads pre, writes the
 // backward gate = (mask/keep) * (pre > 0 ? 1 : 0.2).  Writes nxt, z = l2_normalize(nxt) into the wide
@@ -176,398 +110,6 @@ __global__ __launch_bounds__(256) void dpre_rows_kernel(const float *__restrict_
         if (dE_next) dn = dn + *reinterpret_cast<const f32x4 *>(dE_next + off);
         const f32x4 gt = *reinterpret_cast<const f32x4 *>(gate + off);
         *reinterpret_cast<f32x4 *>(dpre + off) = dn * gt;
-    }
-}
-
-// dA1 = dpre W1^T, dA2 = dpre W2^T;  dside = dA1 + dA2*E ;  dE = dA1 + dA2*side
-// Same structure as dense_fwd_kernel; B[k][j] = W[j][k], so the weights are TRANSPOSED on their way into LDS
-// (s_wt[k][j]) and the B reads are again consecutive lanes on consecutive banks.
-template <int NT>
-__global__ __launch_bounds__(256) void dense_bwd_kernel(const float *__restrict__ dpre, const float *__restrict__ W1,
-                                                        const float *__restrict__ W2, const float *__restrict__ E,
-                                                        const float *__restrict__ side, int64_t n_rows,
-                                                        float *__restrict__ dside, float *__restrict__ dE) {
-    constexpr int LD = 32 * NT, LDP = LD + 1;       // padded rows: the transposing writes below fall on distinct banks
-    extern __shared__ float s_w[];                  // [2][LD][LDP], transposed
-    for (int k = threadIdx.x; k < LD * LD; k += blockDim.x) {
-        const int j = k / LD, c = k % LD;           // coalesced read of W[j][c], write to s_wt[c][j]
-        s_w[c * LDP + j] = W1[k];
-        s_w[LD * LDP + c * LDP + j] = W2[k];
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    const int64_t n_tiles = (n_rows + 31) / 32;
-    for (int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * 4) {
-        const int64_t row0 = tile * 32, row = row0 + r;
-        const int64_t rowc = row < n_rows ? row : n_rows - 1;
-        f32x16 a1[NT], a2[NT];
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) { a1[t][q] = 0.f; a2[t][q] = 0.f; }
-        // the epilogue's E / side values (C layout) are fetched BEFORE the MFMA loop: a wavefront owns a single tile, so
-        // nothing else can hide their latency (62 -> 3x us per call when they were loaded after the products)
-        float ev[NT][16], sv[NT][16];
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) {
-                int64_t orow = row0 + cd_row(q, h);
-                if (orow >= n_rows) orow = n_rows - 1;
-                const int64_t o = orow * LD + 32 * t + r;
-                ev[t][q] = E[o]; sv[t][q] = side[o];
-            }
-#pragma unroll
-        for (int c = 0; c < LD; c += 64) {
-            const int k0 = c + 32 * h;
-            const bool kv = k0 < LD;
-            const int kb = kv ? k0 : 0;
-            const float keep = kv ? 1.f : 0.f;
-            const f32x4 *pg = reinterpret_cast<const f32x4 *>(dpre + rowc * LD + kb);
-            float g[32];
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const f32x4 v = pg[q];
-                g[4 * q] = v.x * keep; g[4 * q + 1] = v.y * keep; g[4 * q + 2] = v.z * keep; g[4 * q + 3] = v.w * keep;
-            }
-#pragma unroll
-            for (int t = 0; t < NT; t++) {
-                const float *w1 = s_w + kb * LDP + 32 * t + r, *w2 = w1 + LD * LDP;
-#pragma unroll
-                for (int s = 0; s < 32; s++) {
-                    a1[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(g[s], w1[s * LDP], a1[t], 0, 0, 0);
-                    a2[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(g[s], w2[s * LDP], a2[t], 0, 0, 0);
-                }
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) {
-                const int64_t orow = row0 + cd_row(q, h);
-                if (orow < n_rows) {
-                    const int64_t o = orow * LD + 32 * t + r;
-                    dside[o] = a1[t][q] + a2[t][q] * ev[t][q];
-                    dE[o] = a1[t][q] + a2[t][q] * sv[t][q];
-                }
-            }
-    }
-}
-
-// =============================================================================================
-// LD <= 64 (NT = 1, 2): the versions that run.  Same products in the same order as dense_fwd_kernel / dense_bwd_kernel
-// above (which stay for ld = 128), but
-//  * the A operand no longer comes from per-lane-row global loads: a 32 x LD tile is fetched with LD/8 fully coalesced
-//    float4 loads per lane (4 whole rows per instruction), parked in a wave-private LDS tile (row stride LD + 4 floats:
-//    the per-row 16-byte reads of the fragment fall on distinct bank groups) and read back in fragment order; the next
-//    tile's global loads are issued before the current tile's MFMA loop;
-//  * the weights never change inside a launch and a wavefront's B fragments of BOTH matrices are only 2 * NT * 32
-//    values per lane, so they live in registers for the whole launch (one wavefront per SIMD, a persistent loop over
-//    tiles): the MFMA loop reads nothing from memory.  (B values read from LDS right before their MFMA -- 64 ds_read2
-//    per tile, the round-1 kernel and the first LDS version -- cost 14 us of the kernel's 25.)
-// Timeline of dense_fwd at the Yelp2018 shape (wall_clock64 stamps per wavefront, 1024 wavefronts, 2179 tiles): weights
-// + first tile 3.6 us, then per tile 0.6 (park / fragment) + 4.5 (128 MFMAs) + 0.9 (stores); every wavefront has two
-// tiles and 131 have a third: 21.4 us, of which 5 are that ragged third round.  Two wavefronts per SIMD without the
-// prefetch: 24.6 us.
-// =============================================================================================
-// (the wavefront tile itself: RowTile, mfma_rows.h)
-
-template <int NT>
-__global__ __launch_bounds__(256) void dense_fwd_lds_kernel(const float *__restrict__ E, const float *__restrict__ side,
-                                                            const float *__restrict__ W1, const float *__restrict__ W2,
-                                                            int64_t n_all, float *__restrict__ pre,
-                                                            const int32_t *__restrict__ row_ids, const int32_t *__restrict__ n_ids) {
-    constexpr int LD = 32 * NT;
-    using Tile = RowTile<LD>;
-    extern __shared__ float s_mem[];                // one tile per wavefront
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    float *tile_mem = s_mem + (threadIdx.x >> 6) * (32 * Tile::RS);
-    const Tile tl(lane);
-    const int kb = 32 * h < LD ? 32 * h : 0;        // ld = 32: the upper k-slot has no columns; its A values are zeros
-    const int64_t n_rows = row_ids ? *n_ids : n_all;            // rows to process: the listed ones, or all
-    const int64_t n_tiles = (n_rows + 31) / 32, stride = (int64_t)gridDim.x * 4;
-    int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    f32x4 e[Tile::NV], sd[Tile::NV];
-    if (tile < n_tiles) { tl.load(E, tile * 32, n_rows, e, row_ids); tl.load(side, tile * 32, n_rows, sd, row_ids); }
-    float b1[NT][32], b2[NT][32];                   // B fragments: W[kb + s][32 t + r]
-#pragma unroll
-    for (int t = 0; t < NT; t++)
-#pragma unroll
-        for (int s = 0; s < 32; s++) {
-            b1[t][s] = W1[(kb + s) * LD + 32 * t + r];
-            b2[t][s] = W2[(kb + s) * LD + 32 * t + r];
-        }
-    for (; tile < n_tiles; tile += stride) {
-        const int64_t row0 = tile * 32;
-        f32x4 t1[Tile::NV], t2[Tile::NV];
-#pragma unroll
-        for (int k = 0; k < Tile::NV; k++) { t1[k] = sd[k] + e[k]; t2[k] = e[k] * sd[k]; }
-        float a1[32], a2[32];
-        tl.park(tile_mem, t1); Tile::fragment(tile_mem, r, h, a1);
-        tl.park(tile_mem, t2); Tile::fragment(tile_mem, r, h, a2);     // same wavefront, LDS operations complete in order
-        if (tile + stride < n_tiles) { tl.load(E, (tile + stride) * 32, n_rows, e, row_ids); tl.load(side, (tile + stride) * 32, n_rows, sd, row_ids); }
-        f32x16 acc[NT];
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) acc[t][q] = 0.f;
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int s = 0; s < 32; s++) {
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b1[t][s], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[s], b2[t][s], acc[t], 0, 0, 0);
-            }
-#pragma unroll
-        for (int q = 0; q < 16; q++) {
-            int64_t orow = row0 + cd_row(q, h);
-            if (orow < n_rows) {
-                if (row_ids) orow = row_ids[orow];
-#pragma unroll
-                for (int t = 0; t < NT; t++) pre[orow * LD + 32 * t + r] = acc[t][q];
-            }
-        }
-    }
-}
-
-// B[k][j] = W[j][k]: lane (r, h) holds W[32 t + r][kb .. kb + 32) of both matrices -- its own row, 8 float4 loads each.
-template <int NT>
-__global__ __launch_bounds__(256) void dense_bwd_lds_kernel(const float *__restrict__ dpre, const float *__restrict__ W1,
-                                                            const float *__restrict__ W2, const float *__restrict__ E,
-                                                            const float *__restrict__ side, int64_t n_all,
-                                                            float *__restrict__ dside, float *__restrict__ dE,
-                                                            const int32_t *__restrict__ row_ids, const int32_t *__restrict__ n_ids) {
-    constexpr int LD = 32 * NT;
-    using Tile = RowTile<LD>;
-    extern __shared__ float s_mem[];                // one tile per wavefront
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    float *tile_mem = s_mem + (threadIdx.x >> 6) * (32 * Tile::RS);
-    const Tile tl(lane);
-    const int kb = 32 * h < LD ? 32 * h : 0;
-    const int64_t n_rows = row_ids ? *n_ids : n_all;
-    const int64_t n_tiles = (n_rows + 31) / 32, stride = (int64_t)gridDim.x * 4;
-    int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    f32x4 gn[Tile::NV];
-    if (tile < n_tiles) tl.load(dpre, tile * 32, n_rows, gn, row_ids);
-    float b1[NT][32], b2[NT][32];
-#pragma unroll
-    for (int t = 0; t < NT; t++)
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const f32x4 v1 = *reinterpret_cast<const f32x4 *>(W1 + (32 * t + r) * LD + kb + 4 * q);
-            const f32x4 v2 = *reinterpret_cast<const f32x4 *>(W2 + (32 * t + r) * LD + kb + 4 * q);
-            b1[t][4 * q] = v1.x; b1[t][4 * q + 1] = v1.y; b1[t][4 * q + 2] = v1.z; b1[t][4 * q + 3] = v1.w;
-            b2[t][4 * q] = v2.x; b2[t][4 * q + 1] = v2.y; b2[t][4 * q + 2] = v2.z; b2[t][4 * q + 3] = v2.w;
-        }
-    for (; tile < n_tiles; tile += stride) {
-        const int64_t row0 = tile * 32;
-        float g[32];
-        tl.park(tile_mem, gn); Tile::fragment(tile_mem, r, h, g);
-        // the epilogue's E / side values (C layout: 128-byte runs) and the next tile go out before the MFMA loop
-        float ev[NT][16], sv[NT][16];
-        int64_t prow[16];                              // physical rows of this lane's 16 output rows
-#pragma unroll
-        for (int q = 0; q < 16; q++) {
-            int64_t orow = row0 + cd_row(q, h);
-            if (orow >= n_rows) orow = n_rows - 1;
-            prow[q] = row_ids ? (int64_t)row_ids[orow] : orow;
-        }
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) {
-                const int64_t o = prow[q] * LD + 32 * t + r;
-                ev[t][q] = E[o]; sv[t][q] = side[o];
-            }
-        if (tile + stride < n_tiles) tl.load(dpre, (tile + stride) * 32, n_rows, gn, row_ids);
-        f32x16 a1[NT], a2[NT];
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) { a1[t][q] = 0.f; a2[t][q] = 0.f; }
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int s = 0; s < 32; s++) {
-                a1[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(g[s], b1[t][s], a1[t], 0, 0, 0);
-                a2[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(g[s], b2[t][s], a2[t], 0, 0, 0);
-            }
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) {
-                if (row0 + cd_row(q, h) < n_rows) {
-                    const int64_t o = prow[q] * LD + 32 * t + r;
-                    dside[o] = a1[t][q] + a2[t][q] * ev[t][q];
-                    dE[o] = a1[t][q] + a2[t][q] * sv[t][q];
-                }
-            }
-    }
-}
-
-// Weight gradients, LD <= 64.  A block owns kBlockRows rows; its 256 threads fetch a stage of 32 rows of E, side and
-// dpre with coalesced float4 loads (6 per thread) into a double-buffered LDS stage while the previous stage is being
-// multiplied; wavefront w owns the output block (which = w / NT, ti = w % NT) -- 32 rows of gW_which, all LD columns --
-// so nothing is summed across wavefronts.  Per stage and wavefront: 16 k-steps (row 2s + h of the stage), two LDS reads
-// for the A value ((side + E) or E * side at column 32 ti + r), NT for B, NT MFMAs.
-// partial[slab][which][i][j] as before (slab = block), then wgrad_reduce_kernel.
-constexpr int kBlockRows = 128;
-template <int NT>
-__global__ __launch_bounds__(256) void wgrad_lds_kernel(const float *__restrict__ E, const float *__restrict__ side,
-                                                        const float *__restrict__ dpre, int64_t n_all,
-                                                        float *__restrict__ partial, const int32_t *__restrict__ row_ids,
-                                                        const int32_t *__restrict__ n_ids) {
-    constexpr int LD = 32 * NT, RS = LD + kTilePad;
-    const int64_t n_rows = row_ids ? *n_ids : n_all;
-    constexpr int NV = 32 * LD / 4 / 256;          // float4 per thread, array and stage (LD = 64: 2, LD = 32: 1)
-    constexpr int kStage = 3 * 32 * RS;            // floats per stage buffer: E, side, dpre
-    extern __shared__ float s_mem[];               // [2][3][32][RS]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int which = wave / NT, ti = wave % NT;
-    const bool owner = wave < 2 * NT;              // LD = 32: two output blocks, wavefronts 2 and 3 only help fetching
-    const int64_t n0 = (int64_t)blockIdx.x * kBlockRows;
-    f32x4 ve[NV], vs[NV], vd[NV];
-    auto fetch = [&](int st) {
-#pragma unroll
-        for (int k = 0; k < NV; k++) {
-            const int idx = threadIdx.x + 256 * k, row = idx / (LD / 4), c4 = 4 * (idx % (LD / 4));
-            int64_t n = n0 + 32 * st + row;
-            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            if (n < n_rows) {
-                if (row_ids) n = row_ids[n];
-                ve[k] = *reinterpret_cast<const f32x4 *>(E + n * LD + c4);
-                vs[k] = *reinterpret_cast<const f32x4 *>(side + n * LD + c4);
-                vd[k] = *reinterpret_cast<const f32x4 *>(dpre + n * LD + c4);
-            } else { ve[k] = zero; vs[k] = zero; vd[k] = zero; }      // rows past the end contribute 0
-        }
-    };
-    auto park = [&](int buf) {
-        float *b = s_mem + buf * kStage;
-#pragma unroll
-        for (int k = 0; k < NV; k++) {
-            const int idx = threadIdx.x + 256 * k, row = idx / (LD / 4), c4 = 4 * (idx % (LD / 4));
-            *reinterpret_cast<f32x4 *>(b + row * RS + c4) = ve[k];
-            *reinterpret_cast<f32x4 *>(b + 32 * RS + row * RS + c4) = vs[k];
-            *reinterpret_cast<f32x4 *>(b + 64 * RS + row * RS + c4) = vd[k];
-        }
-    };
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; t++)
-#pragma unroll
-        for (int q = 0; q < 16; q++) acc[t][q] = 0.f;
-    constexpr int kStages = kBlockRows / 32;
-    fetch(0); park(0);
-    __syncthreads();
-    for (int st = 0; st < kStages; st++) {
-        const bool more = st + 1 < kStages && n0 + 32 * (st + 1) < n_rows;
-        if (more) fetch(st + 1);
-        if (owner) {
-            const float *b = s_mem + (st & 1) * kStage;
-            const float *pe = b + h * RS + 32 * ti + r, *ps = pe + 32 * RS, *pd = b + 64 * RS + h * RS + r;
-#pragma unroll
-            for (int s = 0; s < 16; s++) {
-                const float e = pe[2 * s * RS], sd = ps[2 * s * RS];
-                const float a = which == 0 ? sd + e : e * sd;
-#pragma unroll
-                for (int t = 0; t < NT; t++)
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, pd[2 * s * RS + 32 * t], acc[t], 0, 0, 0);
-            }
-        }
-        if (more) park((st + 1) & 1);
-        __syncthreads();
-        if (!more) break;
-    }
-    if (owner) {
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++)
-                partial[(((int64_t)blockIdx.x * 2 + which) * LD + 32 * ti + cd_row(q, h)) * LD + 32 * t + r] = acc[t][q];
-    }
-}
-
-// partial[slab][which][i][j] = sum over the slab's rows n of A_which[n][i] * dpre[n][j]
-//   which = 0: A = side + E ; 1: A = E * side.
-// One wavefront per (slab of 128 rows, 32-column block ti of A): it forms BOTH products for ALL NT column tiles of
-// dpre, i.e. 2*NT MFMAs per k-step from 2 + NT coalesced dword loads (the first version issued 3 loads per MFMA from
-// one wavefront per SIMD and sat in load latency: 98 us for 1.1 GFLOP).  A chunk's 32 k-steps are fetched first, then
-// its MFMAs run.  Rows past the end feed a = 0.
-constexpr int kWaveRows = 128;                 // rows one wavefront accumulates (64 gives the same 36 us and doubles the partial slabs)
-constexpr int kSlabRows = 4 * kWaveRows;       // rows per block = per partial slab (4 wavefronts, summed through LDS)
-template <int NT>
-__global__ __launch_bounds__(256) void wgrad_kernel(const float *__restrict__ E, const float *__restrict__ side,
-                                                    const float *__restrict__ dpre, int64_t n_rows,
-                                                    float *__restrict__ partial) {
-    constexpr int LD = 32 * NT;
-    extern __shared__ float s_acc[];               // [4 waves][2*NT tiles][16][64 lanes]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int slab = blockIdx.x, ti = blockIdx.y;
-    const int64_t n0 = (int64_t)slab * kSlabRows + (int64_t)wave * kWaveRows;
-    f32x16 acc[2][NT];
-#pragma unroll
-    for (int w = 0; w < 2; w++)
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) acc[w][t][q] = 0.f;
-    const float *pe = E + 32 * ti + r, *ps = side + 32 * ti + r, *pd = dpre + r;
-    for (int c = 0; c < kWaveRows; c += 64) {
-        float a0[32], a1[32], b[NT][32];
-#pragma unroll
-        for (int s = 0; s < 32; s++) {
-            const int64_t n = n0 + c + 32 * h + s;
-            const int64_t nc = n < n_rows ? n : n_rows - 1;
-            const float keep = n < n_rows ? 1.f : 0.f;
-            const float e = pe[nc * LD], sd = ps[nc * LD];
-            a0[s] = (sd + e) * keep; a1[s] = (e * sd) * keep;
-#pragma unroll
-            for (int t = 0; t < NT; t++) b[t][s] = pd[nc * LD + 32 * t];
-        }
-#pragma unroll
-        for (int s = 0; s < 32; s++)
-#pragma unroll
-            for (int t = 0; t < NT; t++) {
-                acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], b[t][s], acc[0][t], 0, 0, 0);
-                acc[1][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b[t][s], acc[1][t], 0, 0, 0);
-            }
-    }
-    // the block's four wavefronts hold the same tiles over different rows: sum them in wave order (deterministic)
-#pragma unroll
-    for (int w = 0; w < 2; w++)
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) s_acc[((wave * 2 * NT + w * NT + t) * 16 + q) * 64 + lane] = acc[w][t][q];
-    __syncthreads();
-    constexpr int kPerWave = 2 * NT * 16 * 64;     // floats one wavefront deposited
-    for (int k = threadIdx.x; k < kPerWave; k += 256) {
-        const float v = ((s_acc[k] + s_acc[kPerWave + k]) + s_acc[2 * kPerWave + k]) + s_acc[3 * kPerWave + k];
-        const int ln = k & 63, q = (k >> 6) & 15, wt = k >> 10, w = wt / NT, t = wt % NT;
-        partial[(((int64_t)slab * 2 + w) * LD + 32 * ti + cd_row(q, ln >> 5)) * LD + 32 * t + (ln & 31)] = v;
-    }
-}
-
-// gW[which][i][j] = sum_slab partial[slab][which][i][j].  A thread owns four consecutive elements (float4) of one of
-// kSplit slab classes (slabs c, c + kSplit, ...: coalesced 16-byte loads, added in slab order); the kSplit class sums
-// of an element meet in LDS and are added in class order -- deterministic.
-constexpr int kSplit = 16;
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restrict__ partial, int n_slabs, int ld,
-                                                           float *__restrict__ gW1, float *__restrict__ gW2) {
-    __shared__ f32x4 s_part[256];
-    const int n4 = 2 * ld * ld / 4;                                     // float4 elements of [2][ld][ld]
-    const int e4 = blockIdx.x * (256 / kSplit) + threadIdx.x / kSplit, c = threadIdx.x % kSplit;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (e4 < n4)
-        for (int s = c; s < n_slabs; s += kSplit) acc = acc + reinterpret_cast<const f32x4 *>(partial)[(int64_t)s * n4 + e4];
-    s_part[threadIdx.x] = acc;
-    __syncthreads();
-    if (c == 0 && e4 < n4) {
-        f32x4 t = s_part[threadIdx.x];
-#pragma unroll
-        for (int k = 1; k < kSplit; k++) t = t + s_part[threadIdx.x + k];
-        const int per = ld * ld / 4;
-        reinterpret_cast<f32x4 *>(e4 < per ? gW1 : gW2)[e4 < per ? e4 : e4 - per] = t;
     }
 }
 
@@ -714,17 +256,6 @@ __global__ __launch_bounds__(1024) void unique_per_batch_kernel(const int32_t *_
     if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
-// persistent grid of the dense-layer kernels: every block stages the weights in LDS once, so no more blocks than
-// the chip keeps resident (2 per CU; 1 when the weights take 128 KB), and never more than there are 128-row groups
-unsigned dense_grid(int64_t n_rows, int ld, bool one_per_cu = false) {
-    const int64_t groups = (n_rows + 127) / 128;
-    const int64_t resident = ld >= 128 || one_per_cu ? 256 : 512;
-    return (unsigned)(groups < resident ? groups : resident);
-}
-hipError_t allow_big_lds(const void *kernel, size_t bytes) {
-    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 }  // namespace
 
 extern "C" {
@@ -736,21 +267,10 @@ int qrec_ngcf_dense_fwd(const float *d_E, const float *d_side, const float *d_W1
     QREC_REQUIRE(!d_row_ids || (d_n_row_ids && max_row_ids >= 0 && ld <= 64), "qrec_ngcf_dense_fwd: a row subset needs its count, a bound, and ld <= 64");
     const int64_t work_rows = d_row_ids ? max_row_ids : n_rows;
     if (work_rows == 0) return QREC_OK;
-    hipStream_t st = as_stream(stream);
-    const unsigned blocks = dense_grid(n_rows, ld);
-    const size_t lds = (size_t)2 * ld * ld * sizeof(float);
-    const unsigned pblocks = dense_grid(work_rows, ld, true);       // ld <= 64: weights in registers, one wavefront per SIMD
-    const size_t lds_tiles = (size_t)4 * 32 * (ld + kTilePad) * sizeof(float);
-    switch (ld) {
-        case 32: hipLaunchKernelGGL(dense_fwd_lds_kernel<1>, dim3(pblocks), dim3(256), lds_tiles, st, d_E, d_side, d_W1, d_W2, n_rows, d_pre, d_row_ids, d_n_row_ids); break;
-        case 64: hipLaunchKernelGGL(dense_fwd_lds_kernel<2>, dim3(pblocks), dim3(256), lds_tiles, st, d_E, d_side, d_W1, d_W2, n_rows, d_pre, d_row_ids, d_n_row_ids); break;
-        case 128:
-            QREC_HIP_CHECK(allow_big_lds(reinterpret_cast<const void *>(&dense_fwd_kernel<4>), lds));
-            hipLaunchKernelGGL(dense_fwd_kernel<4>, dim3(blocks), dim3(256), lds, st, d_E, d_side, d_W1, d_W2, n_rows, d_pre); break;
-        default: set_error("qrec_ngcf_dense_fwd: row stride must be 32, 64 or 128 floats (got %d)", ld); return QREC_ERR_INVALID;
-    }
-    QREC_LAUNCH_CHECK();
-    return QREC_OK;
+    QREC_REQUIRE(ld == 32 || ld == 64 || ld == 128, "qrec_ngcf_dense_fwd: row stride must be 32, 64 or 128 floats (got %d)", ld);
+    const float *no_residual = nullptr;
+    return launch_layer_fwd<SumProductOps>(as_stream(stream), ld, work_rows, d_E, d_side, d_W1, d_W2, no_residual, n_rows, 0, d_pre,
+                                           d_row_ids, d_n_row_ids);
 }
 
 int qrec_ngcf_activate(float *d_pre_gate, int64_t n_rows, int32_t d, int32_t ld, float keep, const float *d_mask,
@@ -796,40 +316,24 @@ int qrec_ngcf_layer_bwd(const float *d_dE_next, const float *d_dWide, const floa
     blocks = (work_rows + 4 * (64 / LPR) - 1) / (4 * (64 / LPR)); if (blocks > 2048) blocks = 2048;                 \
     hipLaunchKernelGGL((dpre_rows_kernel<LPR>), dim3((unsigned)blocks), dim3(256), 0, st, d_dE_next, d_dWide, d_wide, \
                        wide_ld, col_off, d_inv_norm, d_gate, n_rows, d, d_dpre, d_row_ids, d_n_row_ids, d_wide_row_mask)
-    const unsigned gblocks = dense_grid(work_rows, ld, ld <= 64);   // ld <= 64: weights in registers, one wavefront per SIMD
-    const size_t lds = (size_t)2 * ld * (ld + 1) * sizeof(float);
-    const size_t lds_tiles = (size_t)4 * 32 * (ld + kTilePad) * sizeof(float);
     switch (ld) {
-        case 32: QREC_DP(8); hipLaunchKernelGGL(dense_bwd_lds_kernel<1>, dim3(gblocks), dim3(256), lds_tiles, st, d_dpre, d_W1, d_W2, d_E, d_side, n_rows, d_dside, d_dE, d_row_ids, d_n_row_ids); break;
-        case 64: QREC_DP(16); hipLaunchKernelGGL(dense_bwd_lds_kernel<2>, dim3(gblocks), dim3(256), lds_tiles, st, d_dpre, d_W1, d_W2, d_E, d_side, n_rows, d_dside, d_dE, d_row_ids, d_n_row_ids); break;
-        case 128:
-            QREC_DP(32);
-            QREC_HIP_CHECK(allow_big_lds(reinterpret_cast<const void *>(&dense_bwd_kernel<4>), lds));
-            hipLaunchKernelGGL(dense_bwd_kernel<4>, dim3(gblocks), dim3(256), lds, st, d_dpre, d_W1, d_W2, d_E, d_side, n_rows, d_dside, d_dE); break;
+        case 32: QREC_DP(8); break;
+        case 64: QREC_DP(16); break;
+        case 128: QREC_DP(32); break;
         default: set_error("qrec_ngcf_layer_bwd: row stride must be 32, 64 or 128 floats (got %d)", ld); return QREC_ERR_INVALID;
     }
 #undef QREC_DP
     QREC_LAUNCH_CHECK();
-    const int nt = ld / 32;
-    const int n_slabs = (int)(nt == 4 ? (n_rows + kSlabRows - 1) / kSlabRows : (work_rows + kBlockRows - 1) / kBlockRows);
-    const size_t wlds = nt == 4 ? (size_t)4 * 2 * nt * 16 * 64 * sizeof(float) : (size_t)2 * 3 * 32 * (ld + kTilePad) * sizeof(float);
-    if (nt == 1) hipLaunchKernelGGL(wgrad_lds_kernel<1>, dim3((unsigned)n_slabs), dim3(256), wlds, st, d_E, d_side, d_dpre, n_rows, d_partial, d_row_ids, d_n_row_ids);
-    else if (nt == 2) hipLaunchKernelGGL(wgrad_lds_kernel<2>, dim3((unsigned)n_slabs), dim3(256), wlds, st, d_E, d_side, d_dpre, n_rows, d_partial, d_row_ids, d_n_row_ids);
-    else {
-        QREC_HIP_CHECK(allow_big_lds(reinterpret_cast<const void *>(&wgrad_kernel<4>), wlds));
-        hipLaunchKernelGGL(wgrad_kernel<4>, dim3((unsigned)n_slabs, 4), dim3(256), wlds, st, d_E, d_side, d_dpre, n_rows, d_partial);
-    }
-    QREC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((2 * ld * ld / 4 + 256 / kSplit - 1) / (256 / kSplit))), dim3(256), 0, st,
-                       d_partial, n_slabs, ld, d_gW1, d_gW2);
-    QREC_LAUNCH_CHECK();
-    return QREC_OK;
+    // X[0] = E, X[1] = side: the kernels write dX[0] = dE, dX[1] = dside
+    const int rc = launch_layer_bwd<SumProductOps>(st, ld, work_rows, d_dpre, d_W1, d_W2, d_E, d_side, n_rows, 0, d_dE, d_dside, d_row_ids,
+                                                   d_n_row_ids);
+    if (rc != QREC_OK) return rc;
+    return launch_layer_wgrad<SumProductOps>(st, ld, work_rows, d_E, d_side, d_dpre, n_rows, d_partial, d_row_ids, d_n_row_ids, d_gW1, d_gW2);
 }
 
 int qrec_ngcf_wgrad_partial_bytes(int64_t n_rows, int32_t ld, int64_t *bytes) {
     QREC_REQUIRE(bytes && n_rows >= 0 && ld > 0, "qrec_ngcf_wgrad_partial_bytes: bad argument");
-    const int64_t slab_rows = ld >= 128 ? kSlabRows : kBlockRows;
-    *bytes = ((n_rows + slab_rows - 1) / slab_rows) * 2 * (int64_t)ld * ld * 4;
+    *bytes = wgrad_slabs(n_rows, ld) * 2 * (int64_t)ld * ld * 4;
     return QREC_OK;
 }
 

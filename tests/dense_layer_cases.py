@@ -1,7 +1,7 @@
-"""Shapes and inputs of the direct dense-layer tests (csrc/dense_layer.hip), shared by tests/test_gpu_dense_layer.py (the kernels
+"""Shapes and inputs of the direct dense-layer tests (csrc/dense_layer.hip, and NGCF's instantiations of the same kernels), shared by tests/test_gpu_dense_layer.py (the kernels
 against the float64 mirror) and tests/test_diffusion_cpu.py (the headroom that makes the integer cases exact).  numpy only.
 
-Row counts: each is the smallest at which a loop of the file behaves differently.  layer_grid caps the persistent kernels at
+Row counts: each is the smallest at which a loop of the kernels (csrc/mfma_layer.h) behaves differently.  layer_grid caps the persistent kernels at
 256 blocks x 4 wavefronts = 1,024 tiles of 32 rows = 32,768 rows:
   32,768  fills the capped grid exactly: every wavefront one tile, the prefetch condition false at the boundary
   32,801  two wavefronts take a second tile, the last tile holds one row
@@ -21,6 +21,14 @@ NORM_ROWS = (1, 77, 69669)
 NORM_SHAPES = [(ld, d) for ld in (32, 64, 128) for d in (29, 32, 50, 64, 100, 128) if d <= ld]
 NORM_CASES = [(ld, d, n) for ld, d in NORM_SHAPES for n in NORM_ROWS]
 NORM_REAL_CASES = [(ld, d, n) for ld, d in ((32, 29), (64, 64), (128, 100)) for n in (77, 69669)]
+
+# NGCF's instantiations (pre = (S + E) W1 + (E * S) W2, csrc/ngcf.hip): one forward and one backward per case
+NGCF_EXACT_CASES = [(32, 29, 32801), (64, 64, 32801), (32, 29, 69669), (64, 64, 69669), (128, 100, 8193), (128, 100, 32801)]
+NGCF_REAL_CASES = [(64, 50, 32801), (128, 128, 32801)]
+# (ld, d, table rows, listed rows, the host's bound on the count): a row subset exists at ld <= 64 only.  77 of 1,000 under a bound
+# of 128: the count comes from the device, the bound only sizes the launch.  32,801 of 40,000 under 33,000: the persistent loops
+# wrap under a subset, and slab 257 of the 258 launched lies past the count and must add zeros
+NGCF_SUBSET_CASES = [(ld, d, n, k, bound) for ld, d in ((32, 29), (64, 64)) for n, k, bound in ((1000, 77, 128), (40000, 32801, 33000))]
 
 GUARD_ROWS = 40                      # rows past n in every output table, pre-filled with SENTINEL: must come back untouched
 SENTINEL = np.float32(-12345.0)
@@ -65,6 +73,32 @@ def headroom(t):
         fwd = f1 + (f2 if has2 else 0.0) + (a["R"] if has_r else 0.0)
         out[has2, has_r, relu] = float(max([fwd.max(), dx1.max(), g1.max()] + ([dx2.max(), g2.max()] if has2 else [])))
     return out
+
+
+def ngcf_inputs(ld, d, n, integer):
+    """E, S, the gradient block G (n x d) and W1, W2 (d x d): integers in -2..2, or standard normal with W * 0.3"""
+    rng = np.random.default_rng(4000 * ld + d + n + (0 if integer else 1))
+    f = (lambda *s: rng.integers(-2, 3, s).astype(np.float32)) if integer else (lambda *s: rng.standard_normal(s).astype(np.float32))
+    t = dict(E=f(n, d), S=f(n, d), G=f(n, d), W1=f(d, d), W2=f(d, d))
+    if not integer:
+        t["W1"] *= np.float32(0.3); t["W2"] *= np.float32(0.3)
+    return t
+
+
+def ngcf_subset_ids(n, k):
+    """k distinct rows of an n-row table in shuffled order, and one row that is NOT listed (it pads the id list up to the bound)"""
+    perm = np.random.default_rng(n + k).permutation(n)
+    return perm[:k].astype(np.int32), int(perm[k])
+
+
+def ngcf_headroom(t):
+    """(forward, backward, weight gradient): the largest sum of absolute products over the elements of pre, of dside and dE, and
+    of gW1 and gW2, in float64.  With entries in -2..2: at most 16 d, 12 d and 8 n."""
+    a = {k: np.abs(v.astype(np.float64)) for k, v in t.items()}
+    add, mul = a["S"] + a["E"], a["E"] * a["S"]
+    dA1, dA2 = a["G"] @ a["W1"].T, a["G"] @ a["W2"].T
+    return (float((add @ a["W1"] + mul @ a["W2"]).max()), float(max((dA1 + dA2 * a["E"]).max(), (dA1 + dA2 * a["S"]).max())),
+            float(max((add.T @ a["G"]).max(), (mul.T @ a["G"]).max())))
 
 
 def norm_integer_inputs(ld, d, n):

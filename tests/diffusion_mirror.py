@@ -23,6 +23,17 @@ def layer_bwd(dpre, X1, X2, W):
     return dX[:, :d], (None if X2 is None else dX[:, d:]), X.T @ dpre
 
 
+def ngcf_fwd(E, S, W1, W2):
+    """NGCF's propagation layer before its activation: pre = (S + E) W1 + (E * S) W2"""
+    return (S + E) @ W1 + (E * S) @ W2
+
+
+def ngcf_bwd(dpre, E, S, W1, W2):
+    """(dside, dE, gW1, gW2) of ngcf_fwd; dE without the sparse product's share (A^T dside)"""
+    dA1, dA2 = dpre @ W1.T, dpre @ W2.T
+    return dA1 + dA2 * E, dA1 + dA2 * S, (S + E).T @ dpre, (E * S).T @ dpre
+
+
 # ---- graphs -----------------------------------------------------------------------------------------------------------------------
 def social_matrix(n_users, follower, followee):
     """DiffNet.py:22-29: entry 1 / |followees(follower)| per relation row, duplicates summed (coo -> TF's sparse product)"""

@@ -149,6 +149,37 @@ def test_integer_dense_layer_cases_stay_below_two_to_the_24(ld, d, n):
         assert worst < D.EXACT_LIMIT
 
 
+@pytest.mark.parametrize("ld,d,n", D.NGCF_EXACT_CASES + [c[:3] for c in D.NGCF_SUBSET_CASES])
+def test_integer_ngcf_layer_cases_stay_below_two_to_the_24(ld, d, n):
+    """the same for NGCF's layer, pre = (S + E) W1 + (E * S) W2: |S + E| and |E * S| are at most 4, so the forward stays below 16 d,
+    dside = dA1 + dA2 * E and dE below 4 d + 8 d = 12 d, and the weight gradient below 8 n (557,352 at 69,669 rows).  A row subset
+    sums a part of what is bounded here."""
+    t = D.ngcf_inputs(ld, d, n, integer=True)
+    for a in t.values():
+        assert a.dtype == np.float32 and np.array_equal(a, np.round(a)) and np.abs(a).max() == 2
+    fwd, bwd, wgrad = D.ngcf_headroom(t)
+    assert fwd <= 16 * d and bwd <= 12 * d and wgrad <= 8 * n
+    for what, worst in (("forward", fwd), ("backward", bwd), ("weight gradient", wgrad)):
+        check(f"integer NGCF-layer case: largest sum of |a||b|, {what}", worst, D.EXACT_LIMIT, ctx=(ld, d, n), kind="info")
+    assert 16 * 128 < D.EXACT_LIMIT and 8 * 69669 == 557352 < D.EXACT_LIMIT
+
+
+def test_ngcf_mirror_is_the_backward_of_its_forward():
+    """the float64 formulas the GPU test compares with, against central differences of sum(pre * G)"""
+    rng = np.random.default_rng(9)
+    E, S, G, W1, W2 = (rng.standard_normal(s) for s in ((7, 5), (7, 5), (7, 5), (5, 5), (5, 5)))
+    dside, dE, gW1, gW2 = M.ngcf_bwd(G, E, S, W1, W2)
+    loss = lambda E, S, W1, W2: float((M.ngcf_fwd(E, S, W1, W2) * G).sum())
+    args = [E, S, W1, W2]
+    for k, grad in ((0, dE), (1, dside), (2, gW1), (3, gW2)):
+        num = np.zeros_like(grad)
+        for idx in np.ndindex(grad.shape):
+            hi = [a.copy() for a in args]; lo = [a.copy() for a in args]
+            hi[k][idx] += 1e-6; lo[k][idx] -= 1e-6
+            num[idx] = (loss(*hi) - loss(*lo)) / 2e-6
+        assert rel_err(grad, num) < 1e-8, k
+
+
 @pytest.mark.parametrize("ld,d,n", D.NORM_CASES)
 def test_integer_dpre_norm_cases_stay_below_two_to_the_24(ld, d, n):
     """the same for dpre = (dz - z (z.dz)) inv gate: integers times powers of two, every intermediate far below 2^24"""

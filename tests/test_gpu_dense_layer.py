@@ -1,5 +1,6 @@
 """csrc/dense_layer.hip where its persistent loops and wide paths run: every instantiation of the forward, backward, weight-gradient
 and pointwise kernels against the float64 mirror (tests/diffusion_mirror.py) at the row counts of tests/dense_layer_cases.py.
+Section 5 holds NGCF's instantiations of the same kernels (csrc/ngcf.hip) to the same harness, row subsets included.
 
 Integer cases are bit for bit (np.array_equal, no tolerance): entries in -2..2, so every product and partial sum is an integer
 below 2^24 (tests/test_diffusion_cpu.py checks that headroom) and fp32 is exact whatever the summation tree -- one stale 32-row
@@ -39,10 +40,15 @@ def _guarded(n, ld, body=None):
     return _db(h)
 
 
-def _out(buf, n, d, what, ctx):
-    """read an output table back: guard rows untouched, pad columns zero; returns the n x d body"""
+def _out(buf, n, d, what, ctx, ids=None):
+    """read an output table back: guard rows untouched, pad columns zero; returns the n x d body.  ids: only these rows of the
+    table were to be written -- every other row still holds the sentinel, and the body is the listed rows in list order"""
     h = buf.numpy()
     assert (h[n:] == D.SENTINEL).all(), f"{what}: rows at or past n_rows were written {ctx}"
+    if ids is not None:
+        unlisted = np.ones(n, bool); unlisted[ids] = False
+        assert (h[:n][unlisted] == D.SENTINEL).all(), f"{what}: rows outside the listed subset were written {ctx}"
+        h, n = h[ids], len(ids)
     assert not h[:n, d:].any(), f"{what}: pad columns are not zero {ctx}"
     return h[:n, :d]
 
@@ -281,3 +287,91 @@ def test_workspace_size_steps_with_the_slab_count_and_four_bytes_less_is_refused
                     capi.dense_layer_bwd(x, x, x if nw == 2 else None, w, n, ld, g1, g2, gW, short)
                 for out in (g1, g2, gW):               # refused before any launch: nothing was written
                     assert out is None or (out.numpy() == D.SENTINEL).all()
+
+
+# ---- 5. NGCF's instantiations: pre = (S + E) W1 + (E * S) W2 and its backward ---------------------------------------------------------
+NGCF_OUT = ("pre", "dpre", "dside", "dE", "gW1", "gW2")
+
+
+class _Ngcf:
+    """one (ld, d, n) of qrec_ngcf_dense_fwd / qrec_ngcf_layer_bwd with its tables on the device once.  The backward is driven
+    so that dpre IS the gradient block G: the wide table's block all zero, 1/|nxt| = 1, gate 1 on the d real columns and 0 on
+    the pad, no dE_next -- (dz - z (z.dz)) * inv * gate = dz exactly.  What lies beside the block in the wide gradient is 3."""
+    WIDE_PAD, COL_OFF = 8, 3
+
+    def __init__(self, t, ld, d, n, ids=None, bound=0):
+        from qrec_amd import capi
+        self.ld, self.d, self.n, self.ids = ld, d, n, ids
+        self.ctx = dict(ld=ld, d=d, n=n, listed=None if ids is None else len(ids), bound=bound)
+        dev = lambda a: _db(pad_cols(a, ld))
+        self.E, self.S, self.W1, self.W2 = dev(t["E"]), dev(t["S"]), _db(_pad_w(t["W1"], d, ld)[0]), _db(_pad_w(t["W2"], d, ld)[0])
+        self.wide_ld = d + self.WIDE_PAD
+        dAll = np.full((n, self.wide_ld), 3.0, np.float32); dAll[:, self.COL_OFF:self.COL_OFF + d] = t["G"]
+        self.dAll, self.All = _db(dAll), _db(np.zeros((n, self.wide_ld), np.float32))
+        self.inv, self.gate = _db(np.ones(n, np.float32)), dev(np.ones((n, d), np.float32))
+        self.rows = None
+        if ids is not None:                            # the id list is `bound` long: past the count it names a row that is NOT listed
+            listed, spare = ids
+            self.ids = listed
+            self.rows = capi.RowSubset(bound)
+            self.rows.rows.upload(np.concatenate([listed, np.full(bound - len(listed), spare, np.int32)]))
+            self.rows.count.upload(np.array([len(listed)], np.int32))
+            self.rows.bound = bound
+        f = {k: v.astype(np.float64) for k, v in t.items()}
+        if self.ids is not None:
+            f.update({k: f[k][self.ids] for k in ("E", "S", "G")})
+        dside, dE, gW1, gW2 = M.ngcf_bwd(f["G"], f["E"], f["S"], f["W1"], f["W2"])
+        self.want = dict(pre=M.ngcf_fwd(f["E"], f["S"], f["W1"], f["W2"]), dpre=f["G"], dside=dside, dE=dE, gW1=gW1, gW2=gW2)
+
+    def run(self):
+        """one forward and one backward into fresh sentinel tables: the device's bodies by name (listed rows only, in list order)"""
+        from qrec_amd import capi
+        from qrec_amd.capi import DeviceBuffer
+        ld, d, n, ctx = self.ld, self.d, self.n, self.ctx
+        pre, dpre, dside, dE = (_guarded(n, ld) for _ in range(4))
+        gW1, gW2 = (_db(np.full((ld, ld), D.SENTINEL, np.float32)) for _ in range(2))     # two allocations: not adjacent
+        need = capi.ngcf_wgrad_partial_bytes(n, ld)
+        partial = DeviceBuffer(need + WS_TAIL, np.uint8)
+        partial.fill_bytes(0xA5)
+        capi.ngcf_dense_fwd(self.E, self.S, self.W1, self.W2, n, ld, pre, rows=self.rows)
+        capi.ngcf_layer_bwd(None, self.dAll, self.All, self.wide_ld, self.COL_OFF, self.inv, self.gate, self.E, self.S, self.W1, self.W2,
+                            n, d, ld, dpre, dside, dE, partial, gW1, gW2, rows=self.rows)
+        assert (partial.numpy()[need:] == 0xA5).all(), f"the weight gradient wrote past ngcf_wgrad_partial_bytes {ctx}"
+        got = {k: _out(b, n, d, k, ctx, self.ids) for k, b in (("pre", pre), ("dpre", dpre), ("dside", dside), ("dE", dE))}
+        for k, b in (("gW1", gW1), ("gW2", gW2)):
+            h = b.numpy()
+            assert not h[d:, :].any() and not h[:, d:].any(), f"{k}: pad rows / columns are not zero {ctx}"
+            got[k] = h[:d, :d]
+        assert got.keys() == self.want.keys() == set(NGCF_OUT)
+        return got
+
+    def assert_exact(self, got):
+        for k in NGCF_OUT:
+            bad = np.argwhere(got[k] != self.want[k])
+            assert np.array_equal(got[k], self.want[k]), f"{k}: {len(bad)} entries differ from the float64 mirror, the first at {bad[0].tolist()} {self.ctx}"
+
+
+@pytest.mark.parametrize("ld,d,n", D.NGCF_EXACT_CASES)
+def test_integer_ngcf_layer_is_exact_in_every_instantiation_and_loop(ld, d, n):
+    layer = _Ngcf(D.ngcf_inputs(ld, d, n, integer=True), ld, d, n)
+    layer.assert_exact(layer.run())
+
+
+@pytest.mark.parametrize("ld,d,n", D.NGCF_REAL_CASES)
+def test_real_ngcf_layer_holds_the_bar_in_every_tile_and_weight_block(ld, d, n):
+    layer = _Ngcf(D.ngcf_inputs(ld, d, n, integer=False), ld, d, n)
+    got, want = layer.run(), layer.want
+    assert np.array_equal(got["dpre"], want["dpre"]), "dpre is the gradient block itself"
+    for k in ("pre", "dside", "dE"):
+        check(f"NGCF layer {k}: worst 32-row tile vs the mirror", D.worst_tile(got[k], want[k]), C.GRAD_TOL, ctx=layer.ctx)
+    for k in ("gW1", "gW2"):
+        check(f"NGCF layer {k}: weight block vs the mirror", rel_err(got[k], want[k]), C.GRAD_TOL, ctx=layer.ctx)
+    same_bits(f"NGCF layer ld={ld} d={d} n={n}", got, layer.run())          # the fixed-order claim: a second launch, the same bits
+
+
+@pytest.mark.parametrize("ld,d,n,listed,bound", D.NGCF_SUBSET_CASES)
+def test_integer_ngcf_layer_under_a_row_subset_touches_the_listed_rows_only(ld, d, n, listed, bound):
+    """the count is read on the device (the bound only sizes the launch: the id list names an unlisted row from the count up to the
+    bound), unlisted rows of pre, dside, dE and dpre keep their sentinel, listed rows and the weight gradients are exact"""
+    layer = _Ngcf(D.ngcf_inputs(ld, d, n, integer=True), ld, d, n, ids=D.ngcf_subset_ids(n, listed), bound=bound)
+    layer.assert_exact(layer.run())
