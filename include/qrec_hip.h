@@ -1011,6 +1011,45 @@ int qrec_socialfd_social_pass(double *d_P, double *d_H, int32_t d, int32_t ld, c
                               const int64_t *d_fe_indptr, const int32_t *d_fe_ids, int32_t n_waves, double lr, double eta, double beta,
                               double *d_slots, void *stream);
 
+/* ---- evaluation of the rating models (csrc/rating_eval.hip): base/recommender.py:88-110, every predictForRating --------------
+ * fp64 tables only (dtype must be QREC_F64: anything else returns QREC_ERR_INVALID and launches nothing), no float atomics,
+ * the same bits from launch to launch.  Test pairs are (d_uid[t], d_iid[t]); -1 = a name the training set does not know
+ * (any id outside its table is treated like -1 and never dereferenced).  One wavefront evaluates one pair, lane = column,
+ * in a grid-stride loop of at most QREC_RATING_MAX_BLOCKS workgroups of QREC_RATING_BLOCK_WAVES wavefronts.  A dot product
+ * is one fixed tree; the scalar sums after it are added left to right as the class adds them:
+ *   QREC_RATING_DOT     P[u].Q[i]; only the user known: d_user_mean[u]; only the item: d_item_mean[i]; neither: global_mean
+ *   QREC_RATING_BIASED  ((P[u].Q[i] + mean) + Bi[i]) + Bu[u];                     either side unknown: global_mean (all below)
+ *   QREC_RATING_SVDPP   imp[u].Q[i] + the BIASED value; d_aux = imp [n_users][ld] from qrec_rating_implicit
+ *   QREC_RATING_EUCLID  ((mean + Bi[i]) + Bu[u]) - diff.diff, diff = P[u] - Q[i]
+ *   QREC_RATING_METRIC  ((Bi[i] + Bu[u]) + mean) - ((diff.H).H^T).diff; d_aux = H [d][d], staged in LDS as [d][d | 1];
+ *                       d > QREC_SOCIAL_H_MAX_D returns QREC_ERR_UNSUPPORTED and launches nothing
+ *   QREC_RATING_RSTE    alpha*P[u].Q[i] + ((1-alpha)*sum_f w_f (P[f].Q[i]))/den[u] where den[u] != 0, else P[u].Q[i], over the
+ *                       followee CSR of qrec_rste_sgd_ordered
+ * d_pred[t] receives the UNROUNDED prediction.  Arrays a form does not read may be null.
+ * qrec_rating_implicit: imp[u] = (...((Y[j0] + Y[j1]) + Y[j2])...) / count over d_rated_items[d_rated_indptr[u] ..] in that
+ *   order, for the n users of d_users (each once); rows of other users are left as they are.
+ * qrec_rating_boundary: in place, x > hi -> hi, x < lo -> lo, else Python's round(x, 3) (half to even on the exact decimal
+ *   value of the double).
+ * qrec_rating_errors: d_abs[t] = |r - p|, d_sq[t] = (r - p)*(r - p); qrec_loss_fold adds either array in pair order.      */
+#define QREC_RATING_DOT 0
+#define QREC_RATING_BIASED 1
+#define QREC_RATING_SVDPP 2
+#define QREC_RATING_EUCLID 3
+#define QREC_RATING_METRIC 4
+#define QREC_RATING_RSTE 5
+#define QREC_RATING_BLOCK_WAVES 8
+#define QREC_RATING_MAX_BLOCKS 256
+int qrec_rating_implicit(const double *d_Y, int32_t dtype, int32_t n_items, int32_t d, int32_t ld, const int64_t *d_rated_indptr,
+                         const int32_t *d_rated_items, const int32_t *d_users, int64_t n, int32_t n_users, double *d_imp,
+                         void *stream);
+int qrec_rating_predict(int32_t form, int32_t dtype, const double *d_P, const double *d_Q, int32_t n_users, int32_t n_items, int32_t d,
+                        int32_t ld, const double *d_Bu, const double *d_Bi, const double *d_aux, const int64_t *d_fe_indptr,
+                        const int32_t *d_fe_ids, const double *d_fe_w, const double *d_fe_den, const double *d_user_mean,
+                        const double *d_item_mean, double global_mean, double alpha, const int32_t *d_uid, const int32_t *d_iid,
+                        int64_t n, double *d_pred, void *stream);
+int qrec_rating_boundary(double *d_x, int64_t n, double lo, double hi, void *stream);
+int qrec_rating_errors(const double *d_rating, const double *d_pred, int64_t n, double *d_abs, double *d_sq, void *stream);
+
 /* ---- CDAE: model/ranking/CDAE.py (csrc/autoencoder.hip) -----------------------------------------------------------------
  * The denoising auto-encoder over a whole user row, evaluated only where the reference's dense batch x n_items arithmetic is
  * non-zero.  fp32; tables [rows][ld] with ld a multiple of 32 and columns [nh, ld) zero; the decoder weight is ITEM-MAJOR

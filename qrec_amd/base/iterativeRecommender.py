@@ -219,10 +219,17 @@ class IterativeRecommender(Recommender):
         self.shuffle_training_data()
         return converged
 
-    def rating_performance(self):
+    def rating_performance_host(self):
         res = [[user, item, rating, self.checkRatingBoundary(self.predictForRating(user, item))]
                for user, item, rating in self.data.testData]
         self.measure = Measure.ratingMeasure(res)
+        return self.measure
+
+    def rating_performance(self):
+        ev = self.rating_evaluator()
+        if ev is None:
+            return self.rating_performance_host()
+        self.measure = ev.measure()      # from the device-resident tables: no pair goes through predictForRating
         return self.measure
 
     def ranking_performance(self, epoch):

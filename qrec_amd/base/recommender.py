@@ -103,18 +103,68 @@ class Recommender:
         return round(prediction, 3)
 
     # ---- evaluation -------------------------------------------------------------------------------
-    def evalRatings(self):
+    def rating_evaluator(self):
+        """The engine.RatingEvaluator bound to this model's device tables, or None: the host loops then run.  Only a
+        class whose ``predictForRating`` the evaluator restates returns one."""
+        return None
+
+    def rating_test_pairs(self):
+        """(uid int32[n], iid int32[n], rating float64[n]) of ``testData`` in list order, -1 = a name the training set does
+        not know; built once per instance"""
+        cache = getattr(self, "_rating_pairs", None)
+        if cache is None:
+            rows, user, item = self.data.testData, self.data.user, self.data.item
+            cache = self._rating_pairs = (np.fromiter((user.get(r[0], -1) for r in rows), dtype=np.int32, count=len(rows)),
+                                          np.fromiter((item.get(r[1], -1) for r in rows), dtype=np.int32, count=len(rows)),
+                                          np.fromiter((r[2] for r in rows), dtype=np.float64, count=len(rows)))
+        return cache
+
+    def bind_rating_evaluator(self, form, tables, **buffers):
+        """A RatingEvaluator of ``form`` over the test pairs, the rating scale and the three means, bound to the device
+        buffers the caller's SGD object holds (engine.RatingEvaluator); kept for ``rating_evaluator``.  None on a ranking
+        run, which never predicts a rating."""
+        self._rating_eval = None
+        if self.ranking is not None and self.ranking.isMainOn():
+            return None
+        from ..engine import RatingEvaluator
+        data = self.data
+        um = np.zeros(len(data.user)); im = np.zeros(len(data.item))
+        for name, k in data.user.items():
+            um[k] = data.userMeans[name]
+        for name, k in data.item.items():
+            im[k] = data.itemMeans[name]
+        uid, iid, rating = self.rating_test_pairs()
+        self._rating_eval = RatingEvaluator(form, tables, uid, iid, rating, (data.rScale[0], data.rScale[-1]), um, im, data.globalMean,
+                                            **buffers)
+        return self._rating_eval
+
+    def evalRatings_host(self):
         lines = ["userId  itemId  original  prediction\n"]
         for pos, (user, item, rating) in enumerate(self.data.testData):
             pred = self.checkRatingBoundary(self.predictForRating(user, item))
             self.data.testData[pos].append(pred)
             lines.append(user + " " + item + " " + str(rating) + " " + str(pred) + "\n")
+        self._publish_ratings(lines, Measure.ratingMeasure(self.data.testData))
+
+    def evalRatings(self):
+        ev = self.rating_evaluator()
+        if ev is None:
+            return self.evalRatings_host()
+        lines = ["userId  itemId  original  prediction\n"]
+        testData = self.data.testData
+        for pos, pred in enumerate(ev.predictions().tolist()):
+            user, item, rating = testData[pos][:3]
+            testData[pos].append(pred)
+            lines.append(user + " " + item + " " + str(rating) + " " + str(pred) + "\n")
+        self._publish_ratings(lines, ev.measure())
+
+    def _publish_ratings(self, lines, measure):
         stamp = strftime("%Y-%m-%d %H-%M-%S", localtime(time()))
         outDir = self.output["-dir"]
         if self.isOutput:
             FileIO.writeFile(outDir, self.config["model.name"] + "@" + stamp + "-rating-predictions" + self.foldInfo + ".txt", lines)
             print("The result has been output to ", abspath(outDir), ".")
-        self.measure = Measure.ratingMeasure(self.data.testData)
+        self.measure = measure
         FileIO.writeFile(outDir, self.config["model.name"] + "@" + stamp + "-measure" + self.foldInfo + ".txt", self.measure)
         self.log.add("###Evaluation Results###")
         self.log.add(self.measure)

@@ -188,6 +188,11 @@ _SIGNATURES = {
     "qrec_socialfd_sgd_ordered": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _f64, _f64, _f64, _f64, _f64, _f64,
                                   _vp, _vp],
     "qrec_socialfd_social_pass": [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _f64, _f64, _f64, _vp, _vp],
+    "qrec_rating_implicit": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp],
+    "qrec_rating_predict": [_i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp,
+                            _i64, _vp, _vp],
+    "qrec_rating_boundary": [_vp, _i64, _f64, _f64, _vp],
+    "qrec_rating_errors": [_vp, _vp, _i64, _vp, _vp, _vp],
     "qrec_cdae_workspace_bytes": [_i32, _i32, _vp],
     "qrec_cdae_encode": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "qrec_cdae_decode": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -1609,6 +1614,37 @@ def socialfd_social_pass(d_P, d_H, d: int, ld: int, d_step_user, n_steps: int, d
     """SocialFD's pass over every user's followees; d_slots[edge] = the metric term"""
     _check(load().qrec_socialfd_social_pass(_dp(d_P), _dp(d_H), d, ld, _dp(d_step_user), n_steps, _dp(d_fe_indptr), _dp(d_fe_ids), n_waves,
                                             lr, eta, beta, _dp(d_slots), _sh(stream)))
+
+
+# ---- evaluation of the rating models (csrc/rating_eval.hip): fp64 tables only; ids of -1 = unknown to the training set ------
+RATING_DOT, RATING_BIASED, RATING_SVDPP, RATING_EUCLID, RATING_METRIC, RATING_RSTE = range(6)
+RATING_BLOCK_WAVES, RATING_MAX_BLOCKS = 8, 256        # a launch evaluates at most their product of pairs side by side
+
+
+def rating_implicit(d_Y, dtype: int, n_items: int, d: int, ld: int, d_rated_indptr, d_rated_items, d_users, n: int, n_users: int, d_imp,
+                    stream=None):
+    """SVD++: imp[u] = (sum of Y over the user's rated items, in CSR order) / count, for the n users of d_users"""
+    _check(load().qrec_rating_implicit(_dp(d_Y), dtype, n_items, d, ld, _dp(d_rated_indptr), _dp(d_rated_items), _dp(d_users), n, n_users,
+                                       _dp(d_imp), _sh(stream)))
+
+
+def rating_predict(form: int, dtype: int, d_P, d_Q, n_users: int, n_items: int, d: int, ld: int, d_uid, d_iid, n: int, d_pred,
+                   global_mean: float, d_Bu=None, d_Bi=None, d_aux=None, d_fe_indptr=None, d_fe_ids=None, d_fe_w=None, d_fe_den=None,
+                   d_user_mean=None, d_item_mean=None, alpha: float = 0.0, stream=None):
+    """unrounded predictions of the n test pairs by one of the RATING_* forms (d_aux: imp for SVDPP, H for METRIC)"""
+    _check(load().qrec_rating_predict(form, dtype, _dp(d_P), _dp(d_Q), n_users, n_items, d, ld, _dp(d_Bu), _dp(d_Bi), _dp(d_aux),
+                                      _dp(d_fe_indptr), _dp(d_fe_ids), _dp(d_fe_w), _dp(d_fe_den), _dp(d_user_mean), _dp(d_item_mean),
+                                      global_mean, alpha, _dp(d_uid), _dp(d_iid), n, _dp(d_pred), _sh(stream)))
+
+
+def rating_boundary(d_x, n: int, lo: float, hi: float, stream=None):
+    """checkRatingBoundary in place: clamp to [lo, hi], else Python's round(x, 3)"""
+    _check(load().qrec_rating_boundary(_dp(d_x), n, lo, hi, _sh(stream)))
+
+
+def rating_errors(d_rating, d_pred, n: int, d_abs, d_sq, stream=None):
+    """|r - p| and (r - p)(r - p) per pair, for loss_fold to add in pair order"""
+    _check(load().qrec_rating_errors(_dp(d_rating), _dp(d_pred), n, _dp(d_abs), _dp(d_sq), _sh(stream)))
 
 
 # ---- CDAE (csrc/autoencoder.hip; the list format is described in include/qrec_hip.h) ----------------------------------------

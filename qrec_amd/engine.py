@@ -844,6 +844,150 @@ class SvdppSgd:
                 self.d_Bi.numpy().astype(np.float64))
 
 
+class RatingEvaluator:
+    """evalRatings / rating_performance of the rating models on the device (base/recommender.py:88-110,
+    base/iterativeRecommender.py:103-113): every test pair's ``checkRatingBoundary(predictForRating(u, i))`` and the
+    MAE / RMSE strings of ``Measure.ratingMeasure``, from the tables where the SGD objects keep them.
+
+    ``form`` names the class's predictForRating (capi.RATING_*).  The evaluator BINDS device buffers and copies none:
+    ``tables`` (a DeviceTables), and by keyword ``Bu`` / ``Bi`` (MfSgd.d_Bu / d_Bi), ``Y`` with ``rated`` = (d_indptr,
+    d_items, host indptr) (SvdppSgd), ``H`` (SocialHSgd.d_H), ``followees`` = (d_ptr, d_ids, d_w, d_den) (SocialSgd, RSTE)
+    and ``alpha``.  Its own buffers -- the test pairs, the two mean arrays, predictions, error slots, SVD++'s imp rows --
+    are allocated once.  ``uid`` / ``iid``: the pairs' ids, -1 = a name the training set does not know.  Ids outside
+    [-1, table size), METRIC at d > capi.SOCIAL_H_MAX_D and non-fp64 tables raise ValueError before anything is launched."""
+    FORMS = {"DOT": capi.RATING_DOT, "BIASED": capi.RATING_BIASED, "SVDPP": capi.RATING_SVDPP, "EUCLID": capi.RATING_EUCLID,
+             "METRIC": capi.RATING_METRIC, "RSTE": capi.RATING_RSTE}
+
+    def __init__(self, form, tables: DeviceTables, uid, iid, rating, scale, user_means, item_means, global_mean: float, *,
+                 Bu=None, Bi=None, Y=None, rated=None, H=None, followees=None, alpha: float = 0.0):
+        self.form = self.FORMS[form] if isinstance(form, str) else int(form)
+        if self.form not in self.FORMS.values():
+            raise ValueError(f"unknown rating form {form!r}")
+        if tables.dtype != np.float64:
+            raise ValueError("the rating evaluator runs on fp64 tables")
+        if self.form == capi.RATING_METRIC and tables.d > capi.SOCIAL_H_MAX_D:
+            raise ValueError(f"the METRIC form supports num.factors <= {capi.SOCIAL_H_MAX_D} (the d x d matrix H stays in LDS), got {tables.d}")
+        needs = {capi.RATING_BIASED: (Bu, Bi), capi.RATING_SVDPP: (Bu, Bi, Y, rated), capi.RATING_EUCLID: (Bu, Bi),
+                 capi.RATING_METRIC: (Bu, Bi, H), capi.RATING_RSTE: (followees,)}.get(self.form, ())
+        if any(x is None for x in needs):
+            raise ValueError("the form's device buffers are missing (Bu/Bi, Y and rated, H or followees)")
+        self.t = tables
+        self.lo, self.hi = float(scale[0]), float(scale[-1])
+        self.global_mean, self.alpha = float(global_mean), float(alpha)
+        self.d_Bu, self.d_Bi, self.d_Y, self.d_H = Bu, Bi, Y, H
+        self.d_fe = followees if followees is not None else (None, None, None, None)
+        um = np.ascontiguousarray(user_means, dtype=np.float64); im = np.ascontiguousarray(item_means, dtype=np.float64)
+        if um.shape != (tables.n_users,) or im.shape != (tables.n_items,):
+            raise ValueError("user_means / item_means must have one entry per table row")
+        uid, iid, rating = self._checked_pairs(uid, iid, rating)
+        self.n = n = uid.size
+        up = lambda a: DeviceBuffer.from_numpy(a if a.size else np.zeros(1, a.dtype))
+        self.d_umean, self.d_imean = up(um), up(im)
+        self.d_uid, self.d_iid, self.d_rating = up(uid), up(iid), up(rating)
+        self.d_pred = DeviceBuffer.zeros(max(n, 1), np.float64)
+        self.d_abs = DeviceBuffer(max(n, 1), np.float64); self.d_sq = DeviceBuffer(max(n, 1), np.float64)
+        self.d_sums = DeviceBuffer.zeros(2, np.float64)
+        self.d_imp = self.d_users = None
+        if self.form == capi.RATING_SVDPP:
+            self.d_rated_ptr, self.d_rated_items, host_ptr = rated
+            if np.asarray(host_ptr).size != tables.n_users + 1:
+                raise ValueError("rated: one CSR row per user")
+            self.d_imp = DeviceBuffer.zeros((tables.n_users, tables.ld), np.float64)
+            self._set_users(uid, iid)
+
+    def _checked_pairs(self, uid, iid, rating):
+        uid = np.ascontiguousarray(uid, dtype=np.int32); iid = np.ascontiguousarray(iid, dtype=np.int32)
+        rating = np.ascontiguousarray(rating, dtype=np.float64)
+        if not (uid.ndim == 1 and uid.shape == iid.shape == rating.shape):
+            raise ValueError("uid, iid and rating must be one-dimensional and of one length")
+        if uid.size and (uid.min() < -1 or uid.max() >= self.t.n_users or iid.min() < -1 or iid.max() >= self.t.n_items):
+            raise ValueError(f"test pair ids must lie in [-1, {self.t.n_users}) for users and [-1, {self.t.n_items}) for items")
+        return uid, iid, rating
+
+    def _set_users(self, uid, iid):
+        """SVD++: the distinct users whose imp row a pair reads"""
+        users = np.unique(uid[(uid >= 0) & (iid >= 0)]).astype(np.int32)
+        self.n_test_users = users.size
+        self.d_users = DeviceBuffer.from_numpy(users if users.size else np.zeros(1, np.int32))
+
+    def set_pairs(self, uid, iid, rating):
+        """other test pairs of the SAME count (the buffers are allocated once); bad ids raise and change nothing"""
+        uid, iid, rating = self._checked_pairs(uid, iid, rating)
+        if uid.size != self.n:
+            raise ValueError(f"set_pairs: this evaluator holds {self.n} pairs, got {uid.size}")
+        if self.n:
+            self.d_uid.upload(uid); self.d_iid.upload(iid); self.d_rating.upload(rating)
+            if self.form == capi.RATING_SVDPP:
+                self._set_users(uid, iid)
+
+    @classmethod
+    def from_host(cls, form, P, Q, uid, iid, rating, scale, user_means, item_means, global_mean, *, Bu=None, Bi=None, Y=None,
+                  rated: CSR | None = None, H=None, followees=None, alpha: float = 0.0):
+        """the same evaluator over host arrays, uploaded here (tests and tools); ``rated``: a CSR of every user's train items
+        in userRated order, ``followees``: (ptr, ids, w, den) as social.followee_csr_by_user returns them"""
+        P = np.asarray(P); Q = np.asarray(Q)
+        if P.dtype != np.float64 or Q.dtype != np.float64:
+            raise ValueError("the rating evaluator runs on fp64 tables")
+        form_id = cls.FORMS[form] if isinstance(form, str) else int(form)
+        if form_id == capi.RATING_METRIC and P.shape[1] > capi.SOCIAL_H_MAX_D:
+            raise ValueError(f"the METRIC form supports num.factors <= {capi.SOCIAL_H_MAX_D} (the d x d matrix H stays in LDS), got {P.shape[1]}")
+        t = DeviceTables(P, Q, np.float64)
+        up = lambda a, dt: None if a is None else DeviceBuffer.from_numpy(np.ascontiguousarray(a, dtype=dt) if np.size(a) else np.zeros(1, dt))
+        kw = dict(Bu=up(Bu, np.float64), Bi=up(Bi, np.float64), H=up(H, np.float64), alpha=alpha)
+        if Y is not None:
+            kw["Y"] = DeviceBuffer.from_numpy(t._pad(np.asarray(Y, dtype=np.float64)))
+            kw["rated"] = (up(rated.indptr, np.int64), up(rated.indices, np.int32), rated.indptr)
+        if followees is not None:
+            ptr, ids, w, den = followees
+            kw["followees"] = (up(ptr, np.int64), up(ids, np.int32), up(w, np.float64), up(den, np.float64))
+        return cls(form, t, uid, iid, rating, scale, user_means, item_means, global_mean, **kw)
+
+    def _predict(self, stream=None):
+        """the unrounded predictions into d_pred"""
+        t, aux = self.t, None
+        if self.form == capi.RATING_SVDPP:
+            capi.rating_implicit(self.d_Y, t.code, t.n_items, t.d, t.ld, self.d_rated_ptr, self.d_rated_items, self.d_users,
+                                 self.n_test_users, t.n_users, self.d_imp, stream)
+            aux = self.d_imp
+        elif self.form == capi.RATING_METRIC:
+            aux = self.d_H
+        ptr, ids, w, den = self.d_fe
+        capi.rating_predict(self.form, t.code, t.P, t.Q, t.n_users, t.n_items, t.d, t.ld, self.d_uid, self.d_iid, self.n, self.d_pred,
+                            self.global_mean, self.d_Bu, self.d_Bi, aux, ptr, ids, w, den, self.d_umean, self.d_imean, self.alpha, stream)
+
+    def _run(self, stream=None):
+        self._predict(stream)
+        capi.rating_boundary(self.d_pred, self.n, self.lo, self.hi, stream)
+
+    def raw_predictions(self, stream=None) -> np.ndarray:
+        """float64[n]: predictForRating of every pair, before the clamp and the rounding"""
+        self._predict(stream)
+        return self.d_pred.numpy(stream)[:self.n]
+
+    def predictions(self, stream=None) -> np.ndarray:
+        """float64[n]: checkRatingBoundary(predictForRating(u, i)) of every pair"""
+        self._run(stream)
+        return self.d_pred.numpy(stream)[:self.n]
+
+    def error_sums(self, stream=None):
+        """(sum |r - p|, sum (r - p)^2) over the pairs, each added in pair order like Python's sum()"""
+        self._run(stream)
+        capi.rating_errors(self.d_rating, self.d_pred, self.n, self.d_abs, self.d_sq, stream)
+        self.d_sums.fill_bytes(0, stream)
+        capi.loss_fold(self.d_sums.ptr, self.d_abs, self.n, stream)
+        capi.loss_fold(self.d_sums.ptr + 8, self.d_sq, self.n, stream)
+        s = self.d_sums.numpy(stream)
+        return float(s[0]), float(s[1])
+
+    def measure(self, stream=None):
+        """["MAE:...\\n", "RMSE:...\\n"] as Measure.ratingMeasure forms them (util/measure.py:59-71)"""
+        import math
+        if self.n == 0:
+            return ["MAE:0\n", "RMSE:0\n"]
+        s_abs, s_sq = self.error_sums(stream)
+        return ["MAE:" + str(s_abs / self.n) + "\n", "RMSE:" + str(math.sqrt(s_sq / self.n)) + "\n"]
+
+
 class AlsSolver:
     """Implicit-feedback ALS (model/ranking/WRMF.py:17-67) with both fp64 tables resident: ``X`` (users) and ``Y`` (items) in
     one ``DeviceTables`` (P = X, Q = Y), the rating CSR by user and by item with confidences ``c = alpha * r``, G and the

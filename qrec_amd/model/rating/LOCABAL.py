@@ -37,9 +37,13 @@ class LOCABAL(SocialRecommender):
         self.W = locabal_weights(self)                                     # :26-34, 0 = the user is in no relation
         self.S = locabal_edges(self)                                       # :35-44 in the walk order of :68-69
 
+    def rating_evaluator(self):
+        return getattr(self, "_rating_eval", None)      # bound in trainModel to the tables the SGD object holds
+
     def trainModel(self):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = SocialHSgd(tables, self.data.elemCount(), "LOCABAL", self.S, self.H, W=self.W)
+        self.bind_rating_evaluator("DOT", tables)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()

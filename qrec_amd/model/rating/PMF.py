@@ -13,9 +13,13 @@ class PMF(IterativeRecommender):
     def __init__(self, conf, trainingSet=None, testSet=None, fold="[1]"):
         super().__init__(conf, trainingSet, testSet, fold)
 
+    def rating_evaluator(self):
+        return getattr(self, "_rating_eval", None)      # bound in trainModel to the tables the SGD object holds
+
     def trainModel(self):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = MfSgd(tables, self.data.elemCount(), capi.MF_PMF)
+        self.bind_rating_evaluator("DOT", tables)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()

@@ -25,9 +25,13 @@ class RSTE(SocialRecommender):
         print("alpha: %.3f" % self.alpha)
         print("=" * 80)
 
+    def rating_evaluator(self):
+        return getattr(self, "_rating_eval", None)      # bound in trainModel to the tables the SGD object holds
+
     def trainModel(self):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = SocialSgd(tables, self.data.elemCount(), "RSTE", followee_csr_by_user(self))
+        self.bind_rating_evaluator("RSTE", tables, followees=(sgd.d_fe_ptr, sgd.d_fe_ids, sgd.d_fe_w, sgd.d_den), alpha=self.alpha)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()

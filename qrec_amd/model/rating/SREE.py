@@ -25,9 +25,13 @@ class SREE(SocialRecommender):
         self.Bu = np.random.rand(self.data.trainingSize()[0]) / 10      # SREE.py:22-23
         self.Bi = np.random.rand(self.data.trainingSize()[1]) / 10
 
+    def rating_evaluator(self):
+        return getattr(self, "_rating_eval", None)      # bound in trainModel to the tables the SGD object holds
+
     def trainModel(self):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = SocialSgd(tables, self.data.elemCount(), "SREE", user_steps(self), Bu=self.Bu, Bi=self.Bi)
+        self.bind_rating_evaluator("EUCLID", tables, Bu=sgd.mf.d_Bu, Bi=sgd.mf.d_Bi)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()

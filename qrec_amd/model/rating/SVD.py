@@ -19,9 +19,13 @@ class SVD(IterativeRecommender):
         self.Bu = np.random.rand(self.data.trainingSize()[0]) / 5      # SVD.py:10-11
         self.Bi = np.random.rand(self.data.trainingSize()[1]) / 5
 
+    def rating_evaluator(self):
+        return getattr(self, "_rating_eval", None)      # bound in trainModel to the tables the SGD object holds
+
     def trainModel(self):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = MfSgd(tables, self.data.elemCount(), capi.MF_SVD, self.Bu, self.Bi)
+        self.bind_rating_evaluator("BIASED", tables, Bu=sgd.d_Bu, Bi=sgd.d_Bi)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()

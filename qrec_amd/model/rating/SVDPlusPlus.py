@@ -30,9 +30,14 @@ class SVDPlusPlus(IterativeRecommender):
         self.Bi = np.random.rand(self.data.trainingSize()[1])
         self.Y = np.random.rand(self.data.trainingSize()[1], self.emb_size)
 
+    def rating_evaluator(self):
+        return getattr(self, "_rating_eval", None)      # bound in trainModel to the tables the SGD object holds
+
     def trainModel(self):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = SvdppSgd(tables, self.Y, self.Bu, self.Bi, self.data.rated_csr(), self.data.elemCount())
+        self.bind_rating_evaluator("SVDPP", tables, Bu=sgd.d_Bu, Bi=sgd.d_Bi, Y=sgd.d_Y,
+                                   rated=(sgd.d_indptr, sgd.d_items, self.data.rated_csr().indptr))
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()

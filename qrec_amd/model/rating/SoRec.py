@@ -29,9 +29,13 @@ class SoRec(SocialRecommender):
         print("regZ: %.3f" % self.regZ)
         print("=" * 80)
 
+    def rating_evaluator(self):
+        return getattr(self, "_rating_eval", None)      # bound in trainModel to the tables the SGD object holds
+
     def trainModel(self):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = SocialSgd(tables, self.data.elemCount(), "SoRec", sorec_relations(self), Z=self.Z)
+        self.bind_rating_evaluator("DOT", tables)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()

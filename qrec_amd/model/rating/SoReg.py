@@ -42,10 +42,14 @@ class SoReg(SocialRecommender):
     def sim(self, u, v):
         return (qmath.pearson_sp(self.data.sRow(u), self.data.sRow(v)) + self.social.weight(u, v)) / 2.0
 
+    def rating_evaluator(self):
+        return getattr(self, "_rating_eval", None)      # bound in trainModel to the tables the SGD object holds
+
     def trainModel(self):
         tables = DeviceTables(self.P, self.Q, np.float64)
         steps = user_steps(self, weight=lambda u, v: self.Sim[u][v], followers=True)
         sgd = SocialSgd(tables, self.data.elemCount(), "SoReg", steps)
+        self.bind_rating_evaluator("DOT", tables)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()

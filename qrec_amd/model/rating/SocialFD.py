@@ -36,9 +36,13 @@ class SocialFD(SocialRecommender):
         self.eta = float(eps["-eta"])
         self.beta = float(eps["-beta"])
 
+    def rating_evaluator(self):
+        return getattr(self, "_rating_eval", None)      # bound in trainModel to the tables the SGD object holds
+
     def trainModel(self):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = SocialHSgd(tables, self.data.elemCount(), "SocialFD", socialfd_steps(self), self.H, Bu=self.Bu, Bi=self.Bi)
+        self.bind_rating_evaluator("METRIC", tables, Bu=sgd.d_Bu, Bi=sgd.d_Bi, H=sgd.d_H)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()

@@ -15,9 +15,13 @@ class SocialMF(SocialRecommender):
     def __init__(self, conf, trainingSet=None, testSet=None, relation=None, fold="[1]"):
         super().__init__(conf, trainingSet, testSet, relation, fold)
 
+    def rating_evaluator(self):
+        return getattr(self, "_rating_eval", None)      # bound in trainModel to the tables the SGD object holds
+
     def trainModel(self):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = SocialSgd(tables, self.data.elemCount(), "SocialMF", user_steps(self))
+        self.bind_rating_evaluator("DOT", tables)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()
