@@ -195,6 +195,7 @@ int qrec_bpr_sgd_scheduled_wide(void *d_P, void *d_Q, int64_t n_users, int64_t n
 #define QREC_HW_SC1_ATOMIC 4    /* sc1 loads, f32 atomic-add deltas                       */
 #define QREC_HW_P_RMW 5         /* item-major only: P[u] by sc1 load + sc1 store (racy), Q[i] / Q[j] by atomic deltas */
 #define QREC_HW_PQ_RMW 6        /* item-major only: P[u] and Q[j] by sc1 load + sc1 store (measurements)              */
+#define QREC_HW_FIXED 7         /* item-major only: atomic deltas as 32-bit INTEGER adds on fixed-point tables (see below)          */
 int qrec_bpr_sgd_hogwild(float *d_P, float *d_Q, int64_t n_users, int64_t n_items, int32_t d, int32_t ld, const int32_t *d_u,
                          const int32_t *d_i, const int32_t *d_j, int64_t n, int32_t chunk,
                          int32_t grid_groups, float lr, float regU, float regI, double *d_loss,
@@ -211,7 +212,14 @@ int qrec_bpr_sgd_hogwild(float *d_P, float *d_Q, int64_t n_users, int64_t n_item
  * with sc1 write-through stores instead of atomic deltas -- one atomic row update per triplet instead of two (0.63-0.64 of the
  * HBM roofline instead of 0.43-0.46), at the price that a P[u] update landing between another group's load and store of the same
  * row is lost.  The expected share of such updates is the collision density c = groups in flight x sum_u (n_u / n)^2; the host
- * takes this variant only where c <= 0.01 (qrec_amd/engine.py resolve_p_update; measured Recall@20 gaps by c in DESIGN.md s5.1). */
+ * takes this variant only where c <= 0.01 (qrec_amd/engine.py resolve_p_update; measured Recall@20 gaps by c in DESIGN.md s5.1).
+ * QREC_HW_FIXED: the atomic-delta policy with the deltas added as integers, which the L2 atomic units retire faster than float adds.
+ * The call expects both tables as int32 = rint(x * 2^26) (range +-32, quantum 1.5e-8) and needs d_driver_state: an epoch is
+ * qrec_bpr_fixed_convert_in, this call, qrec_epoch_close_fixed; outside those three the tables are fp32.  Nothing wraps silently: a
+ * value with |x| >= 16 or a NaN, at convert-in or produced by a step, sets d_driver_state[QREC_DRV_FAILED] (the one thing this
+ * variant writes there); the close still writes the tables back as fp32 and the enqueued epochs behind it are no-ops.  An element
+ * out of range at convert-in saturates; one that a step of a failed epoch carried past +-32 (its delta is added in two's complement)
+ * may have wrapped. */
 int qrec_bpr_sgd_hogwild_item_major(float *d_P, float *d_Q, int64_t n_users, int64_t n_items, int32_t d, int32_t ld,
                                     const int32_t *d_u, const int32_t *d_i, const int32_t *d_j, int64_t n, int32_t chunk,
                                     int32_t grid_groups, int32_t flush_every, float lr, float regU, float regI,
@@ -231,7 +239,7 @@ int qrec_bpr_sgd_hogwild_item_major(float *d_P, float *d_Q, int64_t n_users, int
 #define QREC_DRV_LAST_LOSS 1  /* lastLoss                                            */
 #define QREC_DRV_EPOCHS 2     /* epochs closed so far                                */
 #define QREC_DRV_CONVERGED 3  /* 1 once |lastLoss - loss| < tol                      */
-#define QREC_DRV_FAILED 4     /* 1 once the loss is NaN/Inf (the reference exits)    */
+#define QREC_DRV_FAILED 4     /* non-zero once the loss is NaN/Inf (the reference exits), or a QREC_HW_FIXED epoch left its range */
 #define QREC_DRV_WORDS 8
 #define QREC_DRV_LOG_WORDS 8
 #define QREC_STATS_MAX_BLOCKS 256
@@ -240,6 +248,12 @@ int qrec_bpr_sgd_hogwild_item_major(float *d_P, float *d_Q, int64_t n_users, int
 int qrec_epoch_close(const void *d_P, int64_t p_rows, const void *d_Q, int64_t q_rows, int dtype, int32_t ld,
                      double *d_stats, double *d_state, double regU, double regI, double max_lr, double tol,
                      double *d_log, int64_t log_capacity, void *stream);
+/* The epoch boundary of a QREC_HW_FIXED epoch (fp32 tables only).  qrec_bpr_fixed_convert_in: both tables fp32 -> int32 in place,
+ * a no-op once CONVERGED or FAILED.  qrec_epoch_close_fixed: qrec_epoch_close, reading the integers and writing fp32 back in place in
+ * the same pass (no launch more than the float close); sum P*P and sum Q*Q are those of the fp32 values it leaves. */
+int qrec_bpr_fixed_convert_in(float *d_P, int64_t p_rows, float *d_Q, int64_t q_rows, int32_t ld, double *d_state, void *stream);
+int qrec_epoch_close_fixed(float *d_P, int64_t p_rows, float *d_Q, int64_t q_rows, int32_t ld, double *d_stats, double *d_state,
+                           double regU, double regI, double max_lr, double tol, double *d_log, int64_t log_capacity, void *stream);
 /* The two halves, for runs whose loss terms are summed over ranks in between (one process per GPU): qrec_epoch_sums
  * leaves sum P*P / sum Q*Q in d_stats[1..2] (d_state may be NULL; a converged/failed state makes it a no-op), the
  * caller all-reduces d_stats[0..1] (sum(-log sigma) and sum P*P add up over user shards, Q is replicated), and

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libqrec_hip.so")
 
 F32, F64, I32 = 0, 1, 2
-HW_DEFAULT, HW_PLAIN_RMW, HW_SC1_RMW, HW_ATOMIC, HW_SC1_ATOMIC, HW_P_RMW, HW_PQ_RMW = 0, 1, 2, 3, 4, 5, 6
+HW_DEFAULT, HW_PLAIN_RMW, HW_SC1_RMW, HW_ATOMIC, HW_SC1_ATOMIC, HW_P_RMW, HW_PQ_RMW, HW_FIXED = 0, 1, 2, 3, 4, 5, 6, 7
 
 _vp, _i32, _i64, _u64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
 
@@ -66,6 +66,8 @@ _SIGNATURES = {
     "qrec_bpr_sgd_hogwild": [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _vp, C.c_int, _vp, _vp],
     "qrec_bpr_sgd_hogwild_item_major": [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _vp, C.c_int, _vp, _vp],
     "qrec_epoch_close": [_vp, _i64, _vp, _i64, C.c_int, _i32, _vp, _vp, _f64, _f64, _f64, _f64, _vp, _i64, _vp],
+    "qrec_bpr_fixed_convert_in": [_vp, _i64, _vp, _i64, _i32, _vp, _vp],
+    "qrec_epoch_close_fixed": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _f64, _f64, _f64, _f64, _vp, _i64, _vp],
     "qrec_epoch_sums": [_vp, _i64, _vp, _i64, C.c_int, _i32, _vp, _vp, _vp],
     "qrec_epoch_decide": [_vp, _vp, _f64, _f64, _f64, _f64, _vp, _i64, _vp],
     "qrec_epoch_sum_table": [_vp, _i64, C.c_int, _i32, _vp, C.c_int, _vp, _vp],
@@ -1200,7 +1202,8 @@ def zero_rows(d_X, ld: int, rows: RowSubset, stream=None):
 def bpr_sgd_hogwild_item_major(d_P, d_Q, d: int, ld: int, d_u, d_i, d_j, n: int, chunk: int, grid_groups: int,
                                flush_every: int, lr: float, regU: float, regI: float, d_loss, stream=None,
                                d_driver_state=None, p_rows: int | None = None, q_rows: int | None = None, variant: int = HW_DEFAULT):
-    """``variant``: HW_DEFAULT (atomic deltas on P[u] and Q[j]) or HW_P_RMW (P[u] by sc1 load + store: include/qrec_hip.h)"""
+    """``variant``: HW_DEFAULT (atomic deltas on P[u] and Q[j]), HW_P_RMW (P[u] by sc1 load + store) or HW_FIXED (integer atomic deltas on
+    tables that ``bpr_fixed_convert_in`` put into fixed point and ``epoch_close_fixed`` writes back): include/qrec_hip.h"""
     _check(load().qrec_bpr_sgd_hogwild_item_major(_dp(d_P), _dp(d_Q), p_rows or _table_rows(d_P, ld), q_rows or _table_rows(d_Q, ld), d, ld, _dp(d_u), _dp(d_i), _dp(d_j), n, chunk,
                                                   grid_groups, flush_every, lr, regU, regI, _dp(d_loss), variant,
                                                   _dp(d_driver_state), _sh(stream)))
@@ -1214,6 +1217,18 @@ def epoch_close(d_P, p_rows: int, d_Q, q_rows: int, dtype: int, ld: int, d_stats
                 max_lr: float, tol: float, d_log=None, log_capacity: int = 0, stream=None):
     _check(load().qrec_epoch_close(_dp(d_P), p_rows, _dp(d_Q), q_rows, dtype, ld, _dp(d_stats), _dp(d_state), regU, regI,
                                    max_lr, tol, _dp(d_log), log_capacity, _sh(stream)))
+
+
+def bpr_fixed_convert_in(d_P, p_rows: int, d_Q, q_rows: int, ld: int, d_state, stream=None):
+    """both fp32 tables -> int32 = rint(x * 2^26) in place, in front of a HW_FIXED epoch (include/qrec_hip.h)"""
+    _check(load().qrec_bpr_fixed_convert_in(_dp(d_P), p_rows, _dp(d_Q), q_rows, ld, _dp(d_state), _sh(stream)))
+
+
+def epoch_close_fixed(d_P, p_rows: int, d_Q, q_rows: int, ld: int, d_stats, d_state, regU: float, regI: float,
+                      max_lr: float, tol: float, d_log=None, log_capacity: int = 0, stream=None):
+    """``epoch_close`` of a HW_FIXED epoch: the same pass also writes the tables back as fp32"""
+    _check(load().qrec_epoch_close_fixed(_dp(d_P), p_rows, _dp(d_Q), q_rows, ld, _dp(d_stats), _dp(d_state), regU, regI,
+                                         max_lr, tol, _dp(d_log), log_capacity, _sh(stream)))
 
 
 def mt_sample_range(state625: np.ndarray, n: int, k: int) -> np.ndarray:

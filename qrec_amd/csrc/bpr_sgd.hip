@@ -109,13 +109,82 @@ __device__ inline void hw_update_row(TabPtr t, int row, int r, const Row<E> &old
     }
 }
 
+// ---- fixed-point rows (QREC_HW_FIXED, item-major atomic-delta policy only) ----------------------------------------------------
+// The L2 atomic units retire integer adds faster than float adds (tools/ubench/atomics4_u32.hip: the shipped stream alone, 64-byte
+// requests, 0.462 against 0.571 ms).  During a launch a table element is int32 = rint(x * 2^26) (fixed_convert_in_kernel /
+// epoch_close_kernel of reduce.hip convert around the SGD launch; the tables are fp32 at rest): range +-32, quantum 1.5e-8 = the fp32
+// ulp at 0.25-0.5.  A row is loaded as integers and converted; every delta is rint(delta * 2^26) added with an integer atomic, and the
+// copy a group forwards to its own next triplet is old_int + delta_int -- what memory holds when nobody else touched the row -- so a
+// forwarded row and a re-read row are the same bits.  Nothing may wrap: a new value with |x| >= 16 (half the range is headroom for
+// deltas in flight) or a NaN raises the driver's FAILED flag (kFailedFixed).  The scalar codec: common.h.
+template <int E> struct RowI { int32_t v[E]; };
+
+template <int E>
+__device__ inline Row<E> fx_row_to_float(const RowI<E> &q) {
+    Row<E> out;
+#pragma unroll
+    for (int e = 0; e < E; e++) out.v[e] = fx_to_float(q.v[e]);
+    return out;
+}
+
+template <int LPR, int E, int LOADP>
+__device__ inline RowI<E> fx_load_row(TabBuf t, int row, int r) {
+    constexpr int aux = (LOADP == LD_SC1) ? kAuxSc1 : kAuxPlain;
+    const uint32_t off = ((uint32_t)row * (uint32_t)(LPR * E) + (uint32_t)r) * 4u;
+    RowI<E> out;
+#pragma unroll
+    for (int e = 0; e < E; e++) out.v[e] = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(t.rs, (int)(off + 4u * LPR * e), 0, aux);
+    return out;
+}
+template <int LPR, int E, int LOADP>
+__device__ inline RowI<E> fx_load_row(TabPtr t, int row, int r) {
+    const int32_t *p = reinterpret_cast<const int32_t *>(t.base) + (int64_t)row * (LPR * E) + r;
+    RowI<E> out;
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        if constexpr (LOADP == LD_SC1) out.v[e] = __hip_atomic_load(p + LPR * e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else out.v[e] = p[LPR * e];
+    }
+    return out;
+}
+// delta = rint((newv - oldv) * 2^26), added atomically; returns it so that the caller can keep old_int + delta_int
+template <int LPR, int E>
+__device__ inline RowI<E> fx_add_row(TabBuf t, int row, int r, const Row<E> &oldv, const Row<E> &newv) {
+    const uint32_t off = ((uint32_t)row * (uint32_t)(LPR * E) + (uint32_t)r) * 4u;
+    RowI<E> dlt;
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        dlt.v[e] = fx_from_float(newv.v[e] - oldv.v[e]);
+        (void)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(dlt.v[e], t.rs, (int)(off + 4u * LPR * e), 0, 0);
+    }
+    return dlt;
+}
+template <int LPR, int E>
+__device__ inline RowI<E> fx_add_row(TabPtr t, int row, int r, const Row<E> &oldv, const Row<E> &newv) {
+    int32_t *p = reinterpret_cast<int32_t *>(t.base) + (int64_t)row * (LPR * E) + r;
+    RowI<E> dlt;
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        dlt.v[e] = fx_from_float(newv.v[e] - oldv.v[e]);
+        (void)__hip_atomic_fetch_add(p + LPR * e, dlt.v[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return dlt;
+}
+template <int E>
+__device__ inline bool fx_row_out_of_range(const Row<E> &x) {
+    bool bad = false;
+#pragma unroll
+    for (int e = 0; e < E; e++) bad = bad || fx_out_of_range(x.v[e]);
+    return bad;
+}
+
 // Learning rate of a throughput epoch: either the host's value, or -- when `state` is given -- the device-resident
 // bold-driver state written by epoch_close_kernel (reduce.hip; layout in include/qrec_hip.h), so that a whole
 // training run can be enqueued without a host round trip per epoch.  A converged / failed run turns the
 // remaining enqueued epochs into no-ops.
 struct HwRate {
     float lr, regU, regI;
-    const double *state;
+    double *state;      // read by every kernel; the fixed-point flavour also raises its FAILED flag
 };
 __device__ inline bool hw_rate_resolve(const HwRate &rt, float &lr, float &cu, float &ci) {
     lr = rt.lr;
@@ -239,7 +308,8 @@ __global__ __launch_bounds__(256) void bpr_hogwild_kernel(
 // Recall@20 gaps equal to the atomic kernel's; c = 0.033 (160 k users): inside the bar, visibly worse (0.0010 vs 0.0001); c = 0.17
 // (Yelp2018 shape): inside on the planted-community graph with a 10 % loss gap; lastfm under BPR.conf (1.9 k users): -0.019, far outside.
 // So the host selects it by c (engine.resolve_p_update: c <= 0.01), never by shape; bit 1 (Q[j]) is kept for measurements only.
-template <int LPR, int E, typename TAB, int RMW = 0>
+// FIX: the fixed-point rows above (atomic-delta policy only, RMW == 0; needs the device-side driver state).
+template <int LPR, int E, typename TAB, int RMW = 0, bool FIX = false>
 __global__ __launch_bounds__(256) void bpr_hogwild_item_kernel(
     float *__restrict__ P, float *__restrict__ Q, int64_t p_bytes, int64_t q_bytes,
     const int32_t *__restrict__ u_idx, const int32_t *__restrict__ i_idx,
@@ -247,6 +317,7 @@ __global__ __launch_bounds__(256) void bpr_hogwild_item_kernel(
     int64_t groups_active, int flush_every, HwRate rate, double *__restrict__ loss_out) {
     constexpr int GPW = kWave / LPR;
     float lr, cu, ci;
+    static_assert(!FIX || RMW == 0, "fixed-point rows: atomic-delta policy only");
     if (!hw_rate_resolve(rate, lr, cu, ci)) return;
     __shared__ int32_t s_idx[4][GPW][3][kMaxChunk];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -256,6 +327,7 @@ __global__ __launch_bounds__(256) void bpr_hogwild_item_kernel(
     const TAB rsP = TAB::make(P, p_bytes), rsQ = TAB::make(Q, q_bytes);
     float loss = 0.f;
     double loss_acc = 0.0;
+    [[maybe_unused]] bool fx_bad = false;
 
     for (int64_t slot = gid; slot < n_chunks && gid < groups_active; slot += groups_active) {
         const int64_t c = (int64_t)(((unsigned __int128)slot * (unsigned __int128)chunk_stride) % (unsigned __int128)n_chunks);
@@ -273,15 +345,25 @@ __global__ __launch_bounds__(256) void bpr_hogwild_item_kernel(
         int ut = su[0], jt = sj[0];
         constexpr int LDP = (RMW & 1) ? LD_SC1 : LD_PLAIN, LDJ = (RMW & 2) ? LD_SC1 : LD_PLAIN;
         constexpr int UPP = (RMW & 1) ? UP_STORE_SC1 : UP_ATOMIC, UPJ = (RMW & 2) ? UP_STORE_SC1 : UP_ATOMIC;
-        Row<E> pu = hw_load_row<LPR, E, LDP>(rsP, ut, r);
-        Row<E> qj = hw_load_row<LPR, E, LDJ>(rsQ, jt, r);
+        // FIX: the rows carried from triplet to triplet are the integers (pui, qji); they are converted where they are used, so that the
+        // prefetch below stays in flight under the math exactly as the float rows do
+        Row<E> pu, qj;
+        [[maybe_unused]] RowI<E> pui, qji;
+        if constexpr (FIX) { pui = fx_load_row<LPR, E, LDP>(rsP, ut, r); qji = fx_load_row<LPR, E, LDJ>(rsQ, jt, r); }
+        else { pu = hw_load_row<LPR, E, LDP>(rsP, ut, r); qj = hw_load_row<LPR, E, LDJ>(rsQ, jt, r); }
         for (int k = 0; k < len; k++) {
             const int it = si[k];
             if (it != cur_i || since_flush >= flush_every) {
-                if (cur_i >= 0) hw_update_row<LPR, E, UP_ATOMIC>(rsQ, cur_i, r, qi0, qi);
-                qi = hw_load_row<LPR, E, LD_SC1>(rsQ, it, r);      // bypass L1: pick up other runs' flushes
+                if constexpr (FIX) {
+                    if (cur_i >= 0) (void)fx_add_row<LPR, E>(rsQ, cur_i, r, qi0, qi);
+                    qi = fx_row_to_float(fx_load_row<LPR, E, LD_SC1>(rsQ, it, r));
+                } else {
+                    if (cur_i >= 0) hw_update_row<LPR, E, UP_ATOMIC>(rsQ, cur_i, r, qi0, qi);
+                    qi = hw_load_row<LPR, E, LD_SC1>(rsQ, it, r);      // bypass L1: pick up other runs' flushes
+                }
                 qi0 = qi; cur_i = it; since_flush = 0;
             }
+            if constexpr (FIX) { pu = fx_row_to_float(pui); qj = fx_row_to_float(qji); }
             // The next triplet's rows go in flight under this one's math.  The 64-bit addressing flavour (TabPtr) issues them UNCONDITIONALLY
             // (the chunk's last triplet re-reads its own rows, unused): under `if (more)` its loads were if-converted into loads + selects,
             // the selects waited for the loads on the spot (s_waitcnt vmcnt(0) right behind the prefetch) and the software pipelining was
@@ -291,11 +373,13 @@ __global__ __launch_bounds__(256) void bpr_hogwild_item_kernel(
             const bool more = (k + 1 < len);
             int un = ut, jn = jt;
             Row<E> npu = pu, nqj = qj;
+            [[maybe_unused]] RowI<E> npui, nqji;
+            if constexpr (FIX) { npui = pui; nqji = qji; }
             if (TAB::kPrefetchAlways || more) {
                 const int kn = more ? k + 1 : k;
                 un = su[kn]; jn = sj[kn];
-                npu = hw_load_row<LPR, E, LDP>(rsP, un, r);
-                nqj = hw_load_row<LPR, E, LDJ>(rsQ, jn, r);
+                if constexpr (FIX) { npui = fx_load_row<LPR, E, LDP>(rsP, un, r); nqji = fx_load_row<LPR, E, LDJ>(rsQ, jn, r); }
+                else { npu = hw_load_row<LPR, E, LDP>(rsP, un, r); nqj = hw_load_row<LPR, E, LDJ>(rsQ, jn, r); }
             }
             float di = 0.f, dj = 0.f;
 #pragma unroll
@@ -311,22 +395,40 @@ __global__ __launch_bounds__(256) void bpr_hogwild_item_kernel(
                 qi.v[e] = a - ci * a; qjn.v[e] = b - ci * b;
                 pun.v[e] = p1 - cu * p1;
             }
-            hw_update_row<LPR, E, UPP>(rsP, ut, r, pu, pun);
-            hw_update_row<LPR, E, UPJ>(rsQ, jt, r, qj, qjn);
+            if constexpr (FIX) {
+                const RowI<E> dp = fx_add_row<LPR, E>(rsP, ut, r, pu, pun), dq = fx_add_row<LPR, E>(rsQ, jt, r, qj, qjn);
+#pragma unroll
+                for (int e = 0; e < E; e++) { pui.v[e] += dp.v[e]; qji.v[e] += dq.v[e]; }     // what memory holds now, this group alone
+                fx_bad = fx_bad || fx_row_out_of_range(pun) || fx_row_out_of_range(qjn) || fx_row_out_of_range(qi);
+            } else {
+                hw_update_row<LPR, E, UPP>(rsP, ut, r, pu, pun);
+                hw_update_row<LPR, E, UPJ>(rsQ, jt, r, qj, qjn);
+            }
             loss += neg_log_sigmoid(di - dj);
             since_flush++;
             if (more) {   // rows this group just changed supersede the prefetched copy
 #pragma unroll
                 for (int e = 0; e < E; e++) {
-                    if (un == ut) npu.v[e] = pun.v[e];
-                    if (jn == jt) nqj.v[e] = qjn.v[e]; else if (jn == cur_i) nqj.v[e] = qi.v[e];
+                    if constexpr (FIX) {
+                        if (un == ut) npui.v[e] = pui.v[e];
+                        if (jn == jt) nqji.v[e] = qji.v[e]; else if (jn == cur_i) nqji.v[e] = fx_from_float(qi.v[e]);
+                    } else {
+                        if (un == ut) npu.v[e] = pun.v[e];
+                        if (jn == jt) nqj.v[e] = qjn.v[e]; else if (jn == cur_i) nqj.v[e] = qi.v[e];
+                    }
                 }
             }
-            pu = npu; qj = nqj; ut = un; jt = jn;
+            if constexpr (FIX) { pui = npui; qji = nqji; }
+            else { pu = npu; qj = nqj; }
+            ut = un; jt = jn;
         }
-        if (cur_i >= 0) hw_update_row<LPR, E, UP_ATOMIC>(rsQ, cur_i, r, qi0, qi);
+        if constexpr (FIX) { if (cur_i >= 0) (void)fx_add_row<LPR, E>(rsQ, cur_i, r, qi0, qi); }
+        else { if (cur_i >= 0) hw_update_row<LPR, E, UP_ATOMIC>(rsQ, cur_i, r, qi0, qi); }
         loss_acc += (double)loss; loss = 0.f;
         __builtin_amdgcn_wave_barrier();
+    }
+    if constexpr (FIX) {
+        if (fx_bad) rate.state[QREC_DRV_FAILED] = kFailedFixed;       // a plain vector store; every writer writes the same value
     }
     if (r != 0) loss_acc = 0.0;
 #pragma unroll
@@ -350,20 +452,24 @@ int launch_hogwild_item(float *P, float *Q, int64_t pb, int64_t qb, const int32_
     auto gcd = [](int64_t a, int64_t b) { while (b) { int64_t t = a % b; a = b; b = t; } return a; };
     while (gcd(stride, n_chunks) != 1) stride++;
     const unsigned blocks = (unsigned)((groups + 4 * GPW - 1) / (4 * GPW));
-#define QREC_ITEM_LAUNCH(RMW)                                                                                                     \
+#define QREC_ITEM_LAUNCH(RMW, FIX)                                                                                                   \
     do {                                                                                                                          \
         if (pb < kBufLimit && qb < kBufLimit && !force_64bit_addressing())                                                        \
-            hipLaunchKernelGGL((bpr_hogwild_item_kernel<LPR, E, TabBuf, RMW>), dim3(blocks), dim3(256), 0, st, P, Q, pb, qb, u, i, j, n, \
+            hipLaunchKernelGGL((bpr_hogwild_item_kernel<LPR, E, TabBuf, RMW, FIX>), dim3(blocks), dim3(256), 0, st, P, Q, pb, qb, u, i, j, n, \
                                chunk, n_chunks, stride, groups, flush_every, rate, loss);                                         \
         else                                                                                                                      \
-            hipLaunchKernelGGL((bpr_hogwild_item_kernel<LPR, E, TabPtr, RMW>), dim3(blocks), dim3(256), 0, st, P, Q, pb, qb, u, i, j, n, \
+            hipLaunchKernelGGL((bpr_hogwild_item_kernel<LPR, E, TabPtr, RMW, FIX>), dim3(blocks), dim3(256), 0, st, P, Q, pb, qb, u, i, j, n, \
                                chunk, n_chunks, stride, groups, flush_every, rate, loss);                                         \
     } while (0)
     switch (variant) {
         case QREC_HW_DEFAULT:
-        case QREC_HW_ATOMIC: QREC_ITEM_LAUNCH(0); break;
-        case QREC_HW_P_RMW: QREC_ITEM_LAUNCH(1); break;
-        case QREC_HW_PQ_RMW: QREC_ITEM_LAUNCH(3); break;
+        case QREC_HW_ATOMIC: QREC_ITEM_LAUNCH(0, false); break;
+        case QREC_HW_P_RMW: QREC_ITEM_LAUNCH(1, false); break;
+        case QREC_HW_PQ_RMW: QREC_ITEM_LAUNCH(3, false); break;
+        case QREC_HW_FIXED:
+            if (!rate.state) { set_error("qrec_bpr_sgd_hogwild_item_major: QREC_HW_FIXED needs d_driver_state"); return QREC_ERR_INVALID; }
+            QREC_ITEM_LAUNCH(0, true);
+            break;
         default: set_error("qrec_bpr_sgd_hogwild_item_major: unknown variant %d", variant); return QREC_ERR_INVALID;
     }
 #undef QREC_ITEM_LAUNCH
@@ -430,7 +536,7 @@ int qrec_bpr_sgd_hogwild(float *d_P, float *d_Q, int64_t n_users, int64_t n_item
     QREC_REQUIRE(n_users >= 1 && n_items >= 1, "qrec_bpr_sgd_hogwild: table row counts must be given");
     const int64_t full_p = n_users * (int64_t)ld * 4, full_q = n_items * (int64_t)ld * 4;
     hipStream_t st = as_stream(stream);
-    const HwRate rate{lr, regU, regI, d_driver_state};
+    const HwRate rate{lr, regU, regI, const_cast<double *>(d_driver_state)};
     switch (ld) {
         case 32: return launch_hogwild<16, 2>(d_P, d_Q, full_p, full_q, d_u, d_i, d_j, n, chunk, grid_groups, rate, d_loss, variant, st);
         case 64: return launch_hogwild<16, 4>(d_P, d_Q, full_p, full_q, d_u, d_i, d_j, n, chunk, grid_groups, rate, d_loss, variant, st);
@@ -454,7 +560,7 @@ int qrec_bpr_sgd_hogwild_item_major(float *d_P, float *d_Q, int64_t n_users, int
     QREC_REQUIRE(n_users >= 1 && n_items >= 1, "qrec_bpr_sgd_hogwild_item_major: table row counts must be given");
     const int64_t full_p = n_users * (int64_t)ld * 4, full_q = n_items * (int64_t)ld * 4;
     hipStream_t st = as_stream(stream);
-    const HwRate rate{lr, regU, regI, d_driver_state};
+    const HwRate rate{lr, regU, regI, const_cast<double *>(d_driver_state)};
     switch (ld) {
         case 32: return launch_hogwild_item<16, 2>(d_P, d_Q, full_p, full_q, d_u, d_i, d_j, n, chunk, grid_groups, flush_every, rate, d_loss, variant, st);
         case 64: return launch_hogwild_item<16, 4>(d_P, d_Q, full_p, full_q, d_u, d_i, d_j, n, chunk, grid_groups, flush_every, rate, d_loss, variant, st);

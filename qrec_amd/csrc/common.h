@@ -188,6 +188,20 @@ __device__ inline double block_sum_fixed(double v, double *lds) {
     return lds[0];
 }
 
+// Fixed-point table elements of the BPR throughput epoch (QREC_HW_FIXED: bpr_sgd.hip, reduce.hip): int32 = rint(x * 2^26) while an
+// epoch's launches run, fp32 at rest.  Range +-32, quantum 2^-26; |x| >= kFixLimit (half the range: headroom for deltas in flight) or
+// a NaN fails the run.  The float is clamped before it is converted (one v_med3_f32; a NaN comes out as the lower bound), so the
+// conversion itself is defined for every input and saturates: a table element out of range at convert-in never wraps.  A DELTA is
+// converted the same way but added in two's complement: an element can only be carried past +-32 by a step that produced |new| >= 16
+// first, which raises FAILED -- such an element may wrap in memory, never silently.
+// QREC_DRV_FAILED = kFailedFixed: "failed while the tables hold integers" -- raised by the epoch's own launches only, and turned into
+// 1 by the epoch close once it has written the tables back as fp32.
+constexpr float kFixScale = 67108864.f, kFixInv = 1.f / 67108864.f, kFixLimit = 16.f;
+constexpr double kFailedFixed = 2.0;
+__device__ inline int32_t fx_from_float(float x) { return __float2int_rn(__builtin_amdgcn_fmed3f(x * kFixScale, -2147483648.f, 2147483520.f)); }
+__device__ inline float fx_to_float(int32_t q) { return (float)q * kFixInv; }
+__device__ inline bool fx_out_of_range(float x) { return !(fabsf(x) < kFixLimit); }      // true for a NaN as well
+
 // index of item in the ascending row[0, len), or -1
 template <typename Len>
 __device__ inline Len sorted_find(const int32_t *__restrict__ row, Len len, int item) {

@@ -2,6 +2,8 @@
 // regU*(P*P).sum() + regI*(Q*Q).sum()).  Pure streaming read: 4 B/element, 16 B per lane per
 // load.  The pad columns [d, ld) of a table are zero by contract (include/qrec_hip.h), so
 // the whole [rows x ld] block is summed without any column test.
+#include <type_traits>
+
 #include "common.h"
 
 using namespace qrec;
@@ -82,17 +84,67 @@ __device__ inline double block_sumsq(const T *__restrict__ x, int64_t n_elems, d
     return s_part[0] + s_part[1] + s_part[2] + s_part[3];
 }
 
-template <typename T, typename V4>
-__global__ __launch_bounds__(256) void epoch_close_kernel(const T *__restrict__ P, int64_t p_elems,
-                                                          const T *__restrict__ Q, int64_t q_elems,
+// ---- fixed-point epoch (QREC_HW_FIXED; the codec: common.h) --------------------------------------------------------------------
+// Convert-in: both fp32 tables -> int32 = rint(x * 2^26), in place, in front of the epoch's SGD launch.  A value out of range or
+// not finite raises the FAILED flag with kFailedFixed (a plain store); it is still converted (saturated), because every block must
+// finish its share whatever another block found: the tables are all-integer until the close writes them back.  For the same reason
+// the kernel does not stop at kFailedFixed, which only this epoch's own launches can have raised.
+__device__ inline bool fixed_convert_in_table(float *__restrict__ x, int64_t n_elems) {
+    bool bad = false;
+    const int64_t n4 = n_elems >> 2;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n4; k += (int64_t)gridDim.x * blockDim.x) {
+        const float4 v = reinterpret_cast<const float4 *>(x)[k];
+        bad = bad || fx_out_of_range(v.x) || fx_out_of_range(v.y) || fx_out_of_range(v.z) || fx_out_of_range(v.w);
+        reinterpret_cast<int4 *>(x)[k] = make_int4(fx_from_float(v.x), fx_from_float(v.y), fx_from_float(v.z), fx_from_float(v.w));
+    }
+    return bad;
+}
+__global__ __launch_bounds__(256) void fixed_convert_in_kernel(float *__restrict__ P, int64_t p_elems, float *__restrict__ Q,
+                                                               int64_t q_elems, double *__restrict__ state) {
+    if (state[QREC_DRV_CONVERGED] != 0.0 || state[QREC_DRV_FAILED] == 1.0) return;
+    const bool bad_p = fixed_convert_in_table(P, p_elems), bad_q = fixed_convert_in_table(Q, q_elems);
+    if (bad_p || bad_q) state[QREC_DRV_FAILED] = kFailedFixed;
+}
+// Convert-out, inside the epoch close's pass over the tables: reads the integers, writes fp32 in place, and sums the squares of the
+// values it wrote -- what the float close would read from the table it leaves.
+__device__ inline double block_sumsq_fixed_out(float *__restrict__ x, int64_t n_elems, double *s_part) {
+    double acc = 0.0;
+    const int64_t n4 = n_elems >> 2;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n4; k += (int64_t)gridDim.x * blockDim.x) {
+        const int4 q = reinterpret_cast<const int4 *>(x)[k];
+        const float4 v = make_float4(fx_to_float(q.x), fx_to_float(q.y), fx_to_float(q.z), fx_to_float(q.w));
+        reinterpret_cast<float4 *>(x)[k] = v;
+        acc += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, kWave);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
+
+// FIX (fp32 only): the tables hold this epoch's integers and are written back as fp32 on the way (above).  An epoch that failed in
+// fixed point (kFailedFixed) is written back all the same, takes no decision, and leaves FAILED = 1.
+template <typename T, typename V4, bool FIX = false>
+__global__ __launch_bounds__(256) void epoch_close_kernel(std::conditional_t<FIX, T, const T> *__restrict__ P, int64_t p_elems,
+                                                          std::conditional_t<FIX, T, const T> *__restrict__ Q, int64_t q_elems,
                                                           double *__restrict__ stats, double *__restrict__ state,
                                                           double regU, double regI, double max_lr, double tol,
                                                           double *__restrict__ log, int64_t log_capacity, int decide) {
-    if (state && (state[QREC_DRV_CONVERGED] != 0.0 || state[QREC_DRV_FAILED] != 0.0)) return;
+    bool failed_fixed = false;
+    if constexpr (FIX) {
+        const double f = state[QREC_DRV_FAILED];
+        if (state[QREC_DRV_CONVERGED] != 0.0 || f == 1.0) return;
+        failed_fixed = f != 0.0;
+    } else {
+        if (state && (state[QREC_DRV_CONVERGED] != 0.0 || state[QREC_DRV_FAILED] != 0.0)) return;
+    }
     __shared__ double s_part[4];
     __shared__ bool s_last;
-    const double sp = block_sumsq<T, V4>(P, p_elems, s_part);
-    const double sq = block_sumsq<T, V4>(Q, q_elems, s_part);
+    double sp, sq;
+    if constexpr (FIX) { sp = block_sumsq_fixed_out(P, p_elems, s_part); sq = block_sumsq_fixed_out(Q, q_elems, s_part); }
+    else { sp = block_sumsq<T, V4>(P, p_elems, s_part); sq = block_sumsq<T, V4>(Q, q_elems, s_part); }
     // per-block partials in the stats buffer (plain stores, made visible by the fence), ONE same-address
     // atomic per block (the ticket); the last block adds the partials in block order: deterministic sums
     double *part = stats + QREC_STATS_PARTIALS;
@@ -122,6 +174,7 @@ __global__ __launch_bounds__(256) void epoch_close_kernel(const T *__restrict__ 
     if (!(decide & 2)) stats[1] = tp;
     if (!(decide & 4)) stats[2] = tq;
     *ticket = 0u;
+    if (failed_fixed) { state[QREC_DRV_FAILED] = 1.0; stats[0] = 0.0; return; }
     if (decide & 1) driver_decide(stats, state, regU, regI, max_lr, tol, log, log_capacity);
 }
 
@@ -225,6 +278,34 @@ int launch_epoch_close(const void *d_P, int64_t p_rows, const void *d_Q, int64_t
     return QREC_OK;
 }
 }  // namespace
+
+extern "C" int qrec_bpr_fixed_convert_in(float *d_P, int64_t p_rows, float *d_Q, int64_t q_rows, int32_t ld, double *d_state,
+                                         void *stream) {
+    QREC_REQUIRE(d_P && d_Q && d_state && p_rows >= 0 && q_rows >= 0 && ld >= 4 && ld % 4 == 0, "qrec_bpr_fixed_convert_in: bad arguments");
+    const int64_t pe = p_rows * (int64_t)ld, qe = q_rows * (int64_t)ld;
+    int64_t blocks = ((pe > qe ? pe : qe) / 4 + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(fixed_convert_in_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), d_P, pe, d_Q, qe, d_state);
+    QREC_LAUNCH_CHECK();
+    return QREC_OK;
+}
+
+extern "C" int qrec_epoch_close_fixed(float *d_P, int64_t p_rows, float *d_Q, int64_t q_rows, int32_t ld, double *d_stats,
+                                      double *d_state, double regU, double regI, double max_lr, double tol, double *d_log,
+                                      int64_t log_capacity, void *stream) {
+    QREC_REQUIRE(d_P && d_Q && d_stats && d_state && p_rows >= 0 && q_rows >= 0 && ld >= 4 && ld % 4 == 0,
+                 "qrec_epoch_close_fixed: bad arguments");
+    QREC_REQUIRE(log_capacity == 0 || d_log, "qrec_epoch_close_fixed: log capacity without a log");
+    const int64_t pe = p_rows * (int64_t)ld, qe = q_rows * (int64_t)ld;
+    int64_t blocks = ((pe > qe ? pe : qe) / 4 + 255) / 256;
+    if (blocks > QREC_STATS_MAX_BLOCKS) blocks = QREC_STATS_MAX_BLOCKS;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL((epoch_close_kernel<float, float4, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), d_P, pe, d_Q, qe,
+                       d_stats, d_state, regU, regI, max_lr, tol, d_log, log_capacity, 1);
+    QREC_LAUNCH_CHECK();
+    return QREC_OK;
+}
 
 extern "C" int qrec_epoch_close(const void *d_P, int64_t p_rows, const void *d_Q, int64_t q_rows, int dtype, int32_t ld,
                                 double *d_stats, double *d_state, double regU, double regI, double max_lr,

@@ -8,6 +8,8 @@ libqrec_hip.so raises.
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 from . import capi
@@ -131,6 +133,26 @@ def resolve_p_update(user_counts, groups: int = DEFAULT_GROUPS, requested: str =
     if requested != "auto":
         raise ValueError("p_update must be 'auto', 'atomic' or 'rmw'")
     return "rmw" if collision_density(user_counts, groups) <= P_RMW_MAX_COLLISION else "atomic"
+
+
+# How the item-major kernel's atomic deltas are accumulated in a device-driven run (QREC_BPR_ACCUM).  "i32": fixed point -- the tables
+# are int32 = rint(x * 2^26) between the epoch's convert-in pass and its close (QREC_HW_FIXED, include/qrec_hip.h), because the L2
+# atomic units retire integer adds faster than float adds.  "f32": the float deltas.  Only where the whole epoch is the library's own
+# three launches on one GPU: a device-driven run (``start_device_driver``), no ``dist``, item-major, P[u] by atomic deltas, fp32 tables;
+# everything else stays float whatever is asked.  "auto" takes "i32" where it pays, by the figures of the gate measurement
+# (tools/ubench/atomics4_u32.hip, profiles/bpr_fixed_accum.json): the integer adds save ~0.087 ns per triplet, the two conversion passes
+# cost ~0.18 ns per table row, and the gain has to be twice the cost -- n >= FIXED_MIN_TRIPLETS_PER_ROW x (users + items) -- and never on
+# ONE group (asked for, or all that is left once the launcher has clamped the groups to the number of chunks), which is the deterministic
+# sequential recurrence, bit for bit the host-driven loop's, and nowhere near the atomic units' rate.
+FIXED_MIN_TRIPLETS_PER_ROW = 8
+
+
+def resolve_accum(requested: str | None = None) -> str:
+    """"auto", "f32" or "i32" from ``requested`` or QREC_BPR_ACCUM"""
+    r = requested if requested is not None else os.environ.get("QREC_BPR_ACCUM", "auto")
+    if r not in ("auto", "f32", "i32"):
+        raise ValueError("QREC_BPR_ACCUM must be auto, f32 or i32")
+    return r
 
 
 MIN_ROUNDS = 8
@@ -273,6 +295,7 @@ class BprSgd:
         self._consumed = [None, None]        # events: "the SGD kernel that read [d_j, d_j_next] has finished"
         self.d_drv = self.d_log = None
         self._log_capacity = 0
+        self.accum = None                    # None: QREC_BPR_ACCUM decides at each epoch (resolve_accum); "auto" / "f32" / "i32": this object's choice
         if pos is not None:
             srt = pos.sorted_rows()
             self._pos_dev = (DeviceBuffer.from_numpy(srt.indptr), DeviceBuffer.from_numpy(srt.indices))
@@ -468,6 +491,9 @@ class BprSgd:
         # the (one block per CU, persistent) SGD grid arrives skews its placement and costs 30% (0.78 vs 0.59 ms).
         # `end` (after it) frees the negatives buffer for the sampler after next.
         start, end = events if events else (self._own_events[0], self._own_events[1])
+        fixed = dist is None and self.fixed_accum(groups, chunk)
+        if fixed:       # in front of the start event: the event still sits right in front of the SGD grid
+            capi.bpr_fixed_convert_in(t.P, t.n_users, t.Q, t.n_items, t.ld, self.d_drv, stream)
         start.record(stream)
         self._sgd_start = start
         if dist is not None and dist.mode == "sharded":
@@ -502,13 +528,18 @@ class BprSgd:
                     if b + 1 < K:
                         dist.sync_tables(stream)
             else:
-                self._launch_sgd(t.P, t.Q, self.d_u, self.d_i, self.d_j, self.n, chunk, groups, flush_every, regU, regI, variant, stream)
+                self._launch_sgd(t.P, t.Q, self.d_u, self.d_i, self.d_j, self.n, chunk, groups, flush_every, regU, regI, variant, stream,
+                                 fixed=fixed)
         end.record(stream)
         self._consumed[0] = end
         self._own_events.reverse()
         if dist is None:
-            capi.epoch_close(t.P, t.n_users, t.Q, t.n_items, t.code, t.ld, self.d_stats, self.d_drv, regU, regI, max_lr,
-                             tol, self.d_log, self._log_capacity, stream)
+            if fixed:
+                capi.epoch_close_fixed(t.P, t.n_users, t.Q, t.n_items, t.ld, self.d_stats, self.d_drv, regU, regI, max_lr,
+                                       tol, self.d_log, self._log_capacity, stream)
+            else:
+                capi.epoch_close(t.P, t.n_users, t.Q, t.n_items, t.code, t.ld, self.d_stats, self.d_drv, regU, regI, max_lr,
+                                 tol, self.d_log, self._log_capacity, stream)
             return
         if dist.mode == "sharded":      # sum P*P and sum Q*Q are over disjoint row shards: all three terms add over ranks
             capi.epoch_sums(t.P, t.n_users, t.Q, t.n_items, t.code, t.ld, self.d_stats, self.d_drv, stream)
@@ -526,13 +557,27 @@ class BprSgd:
             capi.epoch_sums(t.P, t.n_users, t.Q, t.n_items, t.code, t.ld, self.d_stats, self.d_drv, stream)
         capi.epoch_decide(self.d_stats, self.d_drv, regU, regI, max_lr, tol, self.d_log, self._log_capacity, stream)
 
-    def _launch_sgd(self, P, Q, d_u, d_i, d_j, n, chunk, groups, flush_every, regU, regI, variant, stream, q_rows=None):
+    def fixed_accum(self, groups: int = 0, chunk: int = 32) -> bool:
+        """whether a single-GPU device-driven epoch of this object, launched on ``groups`` groups (0 = the launcher's default) in chunks of
+        ``chunk``, accumulates its deltas as integers (resolve_accum above)"""
+        if not (self.d_drv is not None and self.schedule == "item" and self.p_update == "atomic" and self.t.dtype == np.float32
+                and len(self.batch_bounds) == 2 and self.n > 0):
+            return False
+        accum = resolve_accum(self.accum)
+        if accum != "auto":
+            return accum == "i32"
+        one_group = groups == 1 or self.n <= chunk          # the launcher clamps the groups to the number of chunks
+        return not one_group and self.n >= FIXED_MIN_TRIPLETS_PER_ROW * (self.t.n_users + self.t.n_items)
+
+    def _launch_sgd(self, P, Q, d_u, d_i, d_j, n, chunk, groups, flush_every, regU, regI, variant, stream, q_rows=None, fixed=False):
         """the throughput kernel of the schedule on (P, Q) -- Q is the item table, or a shard's row cache with the
-        triplets' item ids rewritten to its rows; learning rate and stop flags come from the device-side driver"""
+        triplets' item ids rewritten to its rows; learning rate and stop flags come from the device-side driver.  ``fixed``: the
+        tables are in fixed point (``epoch_device_async`` put them there and closes the epoch with ``epoch_close_fixed``)"""
         t = self.t
         if self.schedule == "item":
             capi.bpr_sgd_hogwild_item_major(P, Q, t.d, t.ld, d_u, d_i, d_j, n, chunk, groups, flush_every, 0.0, regU, regI,
-                                            self.d_stats, stream, self.d_drv, p_rows=t.n_users, q_rows=q_rows, variant=self.item_variant)
+                                            self.d_stats, stream, self.d_drv, p_rows=t.n_users, q_rows=q_rows,
+                                            variant=capi.HW_FIXED if fixed else self.item_variant)
         else:
             capi.bpr_sgd_hogwild(P, Q, t.d, t.ld, d_u, d_i, d_j, n, chunk, groups, 0.0, regU, regI, self.d_stats, variant,
                                  stream, self.d_drv, p_rows=t.n_users, q_rows=q_rows)
