@@ -170,12 +170,12 @@ __device__ inline RowI<E> fx_add_row(TabPtr t, int row, int r, const Row<E> &old
     }
     return dlt;
 }
+// the range test as a running maximum of magnitude bits (common.h): folded per triplet, tested once per launch
 template <int E>
-__device__ inline bool fx_row_out_of_range(const Row<E> &x) {
-    bool bad = false;
+__device__ inline uint32_t fx_row_mag(uint32_t mag, const Row<E> &x) {
 #pragma unroll
-    for (int e = 0; e < E; e++) bad = bad || fx_out_of_range(x.v[e]);
-    return bad;
+    for (int e = 0; e < E; e++) mag = max(mag, fx_mag_bits(x.v[e]));
+    return mag;
 }
 
 // Learning rate of a throughput epoch: either the host's value, or -- when `state` is given -- the device-resident
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256) void bpr_hogwild_item_kernel(
     const TAB rsP = TAB::make(P, p_bytes), rsQ = TAB::make(Q, q_bytes);
     float loss = 0.f;
     double loss_acc = 0.0;
-    [[maybe_unused]] bool fx_bad = false;
+    [[maybe_unused]] uint32_t fx_mag = 0;
 
     for (int64_t slot = gid; slot < n_chunks && gid < groups_active; slot += groups_active) {
         const int64_t c = (int64_t)(((unsigned __int128)slot * (unsigned __int128)chunk_stride) % (unsigned __int128)n_chunks);
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(256) void bpr_hogwild_item_kernel(
                 const RowI<E> dp = fx_add_row<LPR, E>(rsP, ut, r, pu, pun), dq = fx_add_row<LPR, E>(rsQ, jt, r, qj, qjn);
 #pragma unroll
                 for (int e = 0; e < E; e++) { pui.v[e] += dp.v[e]; qji.v[e] += dq.v[e]; }     // what memory holds now, this group alone
-                fx_bad = fx_bad || fx_row_out_of_range(pun) || fx_row_out_of_range(qjn) || fx_row_out_of_range(qi);
+                fx_mag = fx_row_mag(fx_row_mag(fx_row_mag(fx_mag, pun), qjn), qi);
             } else {
                 hw_update_row<LPR, E, UPP>(rsP, ut, r, pu, pun);
                 hw_update_row<LPR, E, UPJ>(rsQ, jt, r, qj, qjn);
@@ -407,6 +407,11 @@ __global__ __launch_bounds__(256) void bpr_hogwild_item_kernel(
             loss += neg_log_sigmoid(di - dj);
             since_flush++;
             if (more) {   // rows this group just changed supersede the prefetched copy
+                // FIX: fx_from_float(qi) below serves the rare case jn == cur_i and is if-converted: 16 vector instructions per triplet under
+                // an empty exec mask.  It stays that way.  Both ways of putting it behind a skip -- a branch on jn == cur_i around the whole
+                // row, and a scalar branch on the wavefront's vote in front of this block -- made the compiler schedule selects right behind
+                // the prefetch above, which then waits for its loads on the spot (s_waitcnt vmcnt(0..7) behind the loads) instead of under
+                // the math: measured 2.31 against 2.47 G triplet-updates/s (profiles/bpr_wave_stream.json).
 #pragma unroll
                 for (int e = 0; e < E; e++) {
                     if constexpr (FIX) {
@@ -428,7 +433,7 @@ __global__ __launch_bounds__(256) void bpr_hogwild_item_kernel(
         __builtin_amdgcn_wave_barrier();
     }
     if constexpr (FIX) {
-        if (fx_bad) rate.state[QREC_DRV_FAILED] = kFailedFixed;       // a plain vector store; every writer writes the same value
+        if (fx_mag_out_of_range(fx_mag)) rate.state[QREC_DRV_FAILED] = kFailedFixed;       // a plain vector store; every writer writes the same value
     }
     if (r != 0) loss_acc = 0.0;
 #pragma unroll

@@ -201,6 +201,13 @@ constexpr double kFailedFixed = 2.0;
 __device__ inline int32_t fx_from_float(float x) { return __float2int_rn(__builtin_amdgcn_fmed3f(x * kFixScale, -2147483648.f, 2147483520.f)); }
 __device__ inline float fx_to_float(int32_t q) { return (float)q * kFixInv; }
 __device__ inline bool fx_out_of_range(float x) { return !(fabsf(x) < kFixLimit); }      // true for a NaN as well
+// The same predicate over many values with ONE test at the end: keep the running unsigned maximum of the magnitude bits.  Non-negative
+// floats order as their bit patterns do, and +inf (0x7f800000) and every NaN (above it) have larger magnitude bits than any finite
+// value, so  max_k fx_mag_bits(x_k) >= bits(16.0f)  <=>  some x_k has !(|x_k| < 16): the flag is raised in exactly the same runs.  (A
+// float maximum with abs modifiers would not do: v_max3_f32 drops NaNs.)  Per value: one v_and_b32 and a third of a v_max3_u32.
+constexpr uint32_t kFixLimitBits = 0x41800000u;      // 16.0f
+__device__ inline uint32_t fx_mag_bits(float x) { return __builtin_bit_cast(uint32_t, x) & 0x7fffffffu; }
+__device__ inline bool fx_mag_out_of_range(uint32_t mag) { return mag >= kFixLimitBits; }
 
 // index of item in the ascending row[0, len), or -1
 template <typename Len>

@@ -24,8 +24,16 @@ template <> __device__ inline double dev_exp<double>(double x) { return exp(x); 
 // -log(sigmoid(x)) = softplus(-x), evaluated without forming sigmoid first: in fp32 sigmoid(x)
 // underflows to 0 for x < -88.7 and -log(0) = inf, while the reference's fp64 value (= -x) is
 // finite down to x ~ -745.  Same value to rounding wherever the direct form is finite.
+//
+// The float overload (the throughput kernels of bpr_sgd.hip) is ONE evaluation, log1p(exp(-|x|)) + max(-x, 0), and not the two-armed
+// form of the double overload below: a wavefront of those kernels carries several groups with unrelated x, the compiler keeps the
+// two arms as a real branch on the sign, and with mixed signs both arms run -- 235 of the item-major loop's ~450 vector instructions
+// per triplet.  It is the two-armed form bit for bit: with L = log1pf(expf(-|x|)) >= +0 (expf >= +0, log1pf(+0) = +0),
+//   x >= 0 (and +-0): -|x| = -x, and the added term is max(-x, 0) = +-0, which leaves L as it is (L is never -0);
+//   x < 0:            -|x| = x, and L + (-x) is the arm's -x + L, one commutative add of the same two addends;
+//   x = +inf: 0 + 0;  x = -inf: 0 + inf;  NaN: L is NaN and NaN + 0 is NaN, as the x < 0 arm gave.
 __device__ inline float neg_log_sigmoid(float x) {
-    return x >= 0.f ? log1pf(expf(-x)) : (-x + log1pf(expf(x)));
+    return log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f);
 }
 __device__ inline double neg_log_sigmoid(double x) {
     return x >= 0.0 ? log1p(exp(-x)) : (-x + log1p(exp(x)));
