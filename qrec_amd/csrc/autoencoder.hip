@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const double *__restrict__ lo
 }
 static_assert(kRegBlocks == 256, "loss_kernel reads one regulariser partial per thread");
 
-// ---- S = sigmoid(S + bias[item]) over the transposed score block of the evaluation (eval_topk.hip) ---------------------
+// ---- S = sigmoid(S + bias[item]) over the transposed score block of the evaluation (eval_block.hip) ---------------------
 __global__ __launch_bounds__(256) void sigmoid_bias_kernel(float *__restrict__ S_T, const float *__restrict__ bias, int n_items, int b_pad) {
     const int64_t n = (int64_t)n_items * b_pad;
     for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256)

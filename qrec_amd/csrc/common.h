@@ -38,7 +38,7 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
 constexpr int kWave = 64;  // gfx950 wavefront
 
 // a runtime value -> a template argument, stated once per ladder: `with_x(value, [&](auto c) { kernel<c()> ... })`
-// (with_nc of eval_topk.hip, with_epl of lane_row.h)
+// (with_nc of eval_fused.hip, with_epl of lane_row.h)
 template <int V> using int_c = std::integral_constant<int, V>;
 
 // ---- workspaces: a file states each layout ONCE, as a function (Carver &, shape...) that returns or fills the file's Ws
@@ -83,6 +83,32 @@ int score_block_sigmoid_bias(float *S_T, const float *bias, int n_items, int b_p
 // qrec_score_topk_sparse_row_sigmoid_bias (cfgan.hip), in the place of the MFMA scoring of the block route
 struct SparseRows { const float *W; int ld; const int64_t *indptr; const int32_t *items; const float *vals; };
 int score_block_sparse_rows(float *S_T, const SparseRows &r, int n_items, const int32_t *user_ids, int n_b, int b_pad, hipStream_t st);
+
+// ---- what crosses between the evaluation's translation units: eval_topk.hip (entry points, dispatch) calls the two routes, the
+// fused route's stage (D) calls two launches of the block route.  Kernels stay private to their files.
+// eval_block.hip: score block -> mask -> heap top-N (fp32 and fp64).  item_bias: qrec_score_topk_sigmoid_bias; sparse:
+// qrec_score_topk_sparse_row_sigmoid_bias (then U, V are unused); both fp32 only
+int64_t block_path_bytes(int dtype, int n_items, int n_b);
+int run_score_topk(int dtype, const void *U, const void *V, int ld, int n_items, const int32_t *user_ids, int n_b,
+                   const int64_t *rated_indptr, const int32_t *rated_items, int K, void *scratch, int32_t *ids_out, void *scores_out,
+                   hipStream_t st, const float *item_bias = nullptr, const SparseRows *sparse = nullptr);
+// Where the fp32 score of (item, user b of the batch) goes: S[item * b_pad + (b / 64) * upair_stride + (b % 64) * u_stride].
+struct ScoreLayout { int b_pad; int64_t upair_stride, u_stride; };
+// the block route's transposed block [rows][b_pad]: what its lane-per-user scans read coalesced
+inline ScoreLayout plain_block(int b_pad) { return {b_pad, 64, 1}; }
+// user-major rows [user][row_len], a user's scores contiguous: what the exact per-user walk of a handful of flagged users wants
+inline ScoreLayout user_major_rows(int64_t row_len) { return {1, 64 * row_len, row_len}; }
+// S = V U[user_ids]^T by score_kernel_f32, every wavefront streaming at least min_tiles_per_wave item tiles (fewer users: shorter
+// wavefronts); the users' rated items -> 0 by mask_kernel<float>
+int launch_score_block_f32(const float *U, const float *V, int ld, int n_items, const int32_t *user_ids, int n_b, int min_tiles_per_wave,
+                           float *S, ScoreLayout lay, hipStream_t st);
+int launch_mask_block(const int32_t *user_ids, int n_b, const int64_t *rated_indptr, const int32_t *rated_items, float *S, ScoreLayout lay,
+                      hipStream_t st);
+// eval_fused.hip: threshold -> filter -> select, no B x I block (fp32, ld <= 128)
+bool fused_ok(int dtype, int ld, int n_items, int K);      // one predicate for the scratch-size query and the launch
+int64_t fused_path_bytes(int n_items, int n_b, int ld);
+int run_fused_topk_f32(const float *U, const float *V, int ld, int n_items, const int32_t *user_ids, int n_b, const int64_t *rated_indptr,
+                       const int32_t *rated_sorted, int K, void *scratch, int32_t *ids_out, float *scores_out, hipStream_t st);
 
 // ---- buffer resources: the only way to get 16-byte loads/stores with an explicit cache
 // policy (sc1 = bypass the non-coherent per-XCD caches) and compiler-tracked waitcnts.

@@ -1,4 +1,4 @@
-"""The bound the evaluation's bf16 filter rests on (qrec_amd/csrc/eval_topk.hip, DESIGN.md s4 "Fused evaluation, bf16 route"):
+"""The bound the evaluation's bf16 filter rests on (qrec_amd/csrc/eval_fused.hip, DESIGN.md s4 "Fused evaluation, bf16 route"):
 with u^, v^ the tables rounded to bfloat16 (round to nearest even) and the products accumulated in float32,
     | u^ . v^  -  u . v |  <=  eps = 2^-7 * 1.02 * |u| * |v|
 so an item whose fp32 score reaches tau has a bf16 score >= tau - eps and cannot be filtered out.  The kernel's guarantee is

@@ -1,6 +1,6 @@
 """The decision logic of the fused evaluation's bf16 route, modelled in numpy and attacked with adversarial rounding errors.
 
-The GPU kernels (eval_topk.hip: sample_max_bf16 / threshold_var / score_filter_bf16 / select_topk) implement these steps for a
+The GPU kernels (eval_fused.hip: sample_max_bf16 / threshold_var / score_filter_bf16 / select_topk) implement these steps for a
 user with exact (fp32) scores s_i, approximate (bf16) scores s^_i, |s^_i - s_i| <= eps, rated items masked out:
   1. group maxima of s^ over <= 128 item groups; tau^ = the (N+1)-th largest group maximum whose best item is unrated;
   2. tau = tau^ - eps (N+1 distinct unrated items have s >= tau);  tau_low = tau - eps;  tau <= 0 -> the exact walk;

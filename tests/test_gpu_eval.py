@@ -247,7 +247,7 @@ def test_fused_route_equals_the_block_route(d, N, route, monkeypatch):
 @pytest.mark.parametrize("route", ["bf16", "bf16-sparse-sample"])
 @pytest.mark.parametrize("d,N", [(64, 20), (128, 10)])
 def test_bf16_filter_is_complete_on_adversarial_tables(d, N, route, monkeypatch):
-    """What the bf16 filter's bound (eval_topk.hip, eps = 2^-7 * 1.02 * |u| * max|v|) has to survive on the hardware, not in a
+    """What the bf16 filter's bound (eval_fused.hip, eps = 2^-7 * 1.02 * |u| * max|v|) has to survive on the hardware, not in a
     model of it: item norms spread over six decades (eps is set by the LARGEST item, the deciding scores by small ones), users
     likewise, large cancelling coordinates (sum |u_k v_k| >> |u.v|: the rounding error is large against the score), and clusters
     of items whose fp32 scores sit within a few ulp of each other around every user's threshold.  A candidate the filter drops

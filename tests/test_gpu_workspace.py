@@ -192,7 +192,7 @@ def test_channel_attention_bwd_stays_inside_its_stated_scratch():
     _twice("MHCN channel attention backward rows=300 ld=32", 4 * capi.channel_attention_scratch_floats(), run)
 
 
-# ---- evaluation (csrc/eval_topk.hip): the block layout and the fused layout ------------------------------------------------------------
+# ---- evaluation (csrc/eval_block.hip, csrc/eval_fused.hip): the block layout and the fused layout ------------------------------------------------------------
 def _ranked_inside(what, rk, users, N):
     """the ranker's one call for `users` in a scratch of exactly the bytes the library states for it"""
     from qrec_amd.capi import DeviceBuffer as DB

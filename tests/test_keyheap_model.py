@@ -1,4 +1,4 @@
-"""The identity the evaluation's exact walk uses on the GPU (KeyHeap::sift in qrec_amd/csrc/eval_topk.hip): CPython's
+"""The identity the evaluation's exact walk uses on the GPU (KeyHeap::sift in qrec_amd/csrc/eval_heap.h): CPython's
 heapq._siftup(heap, pos) -- bubble the smaller child up to a leaf, then sift the item back down -- nets out to an insertion
 along the smaller-child path: the path's entries grow downwards, the item passes exactly those smaller than itself (each moves
 up one level) and lands where the next one is larger.  Modelled here in Python next to heapq itself: heapify and heapreplace

@@ -29,7 +29,7 @@ CPU_CASES = (
     + [("random_permutations", [n, c]) for n, c in ((0, 0), (1, 1), (37, 3))]       # small sorts: rocprim sizes them without a device
 )
 
-# ---- the evaluation's scratch (csrc/eval_topk.hip): the one size that depends on switches read per call, so a case carries the
+# ---- the evaluation's scratch (csrc/eval_block.hip, csrc/eval_fused.hip): the one size that depends on switches read per call, so a case carries the
 # environment it is recorded under.  Items: 32-item tile padding, the heap / sliced boundary 8192, the fused boundary 16384;
 # users: 64-padding and the fallback's fb_users = max(n_b / 16, 256) switch at 4096; ld 96 is fused without bf16, 160 never
 # fused; fused needs K + 1 <= 64.  The product is thinned, every value of every axis stays.

@@ -1,8 +1,9 @@
-// Where does exact_walk_lds_kernel (the fused evaluation's exact per-user walk, qrec_amd/csrc/eval_topk.hip) spend its time?
+// Where does exact_walk_lds_kernel (the fused evaluation's exact per-user walk, qrec_amd/csrc/eval_walk.h) spend its time?
 // Phase stamps from the 100 MHz wall clock (staging / heapify / walk), update and group counts, for 1 / 5 / 256 users.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../include -I../../qrec_amd/csrc -o exact_walk_probe exact_walk_probe.hip
 #define QREC_WALK_PROBE
-#include "../../qrec_amd/csrc/eval_topk.hip"
+#include "../../qrec_amd/csrc/eval_walk.h"
+using namespace qrec;
 #include <cstdio>
 #include <random>
 #include <vector>
