@@ -1064,6 +1064,38 @@ int qrec_rating_predict(int32_t form, int32_t dtype, const double *d_P, const do
 int qrec_rating_boundary(double *d_x, int64_t n, double lo, double hi, void *stream);
 int qrec_rating_errors(const double *d_rating, const double *d_pred, int64_t n, double *d_abs, double *d_sq, void *stream);
 
+/* ---- ranking of the rating models (csrc/rank_forms.hip): predictForRanking of SVD, SVDPlusPlus, EE, SREE, RSTE, SocialFD -------
+ * qrec_score_topk's BLOCK route with its scoring step replaced by one of the QREC_RATING_* forms above, fp64, no float atomics,
+ * the same bits from launch to launch; mask (rated items -> 0) and the reference's heap top-N run unchanged, outputs are
+ * [n_batch_users][N] with ids -1-padded when n_items < N.  Score of (user u, item i), mu = the global mean:
+ *   QREC_RATING_DOT     Q[i].P[u]
+ *   QREC_RATING_BIASED  ((Q[i].P[u] + mu) + Bi[i]) + Bu[u]                                                    (SVD.py:88)
+ *   QREC_RATING_SVDPP   the BIASED value on the row P[u] + (sum_j Y[j]) / w over d_y_items[d_y_indptr[u] ..] in that order
+ *                       (userRated order; w = the row's length, w = 0: P[u] alone)                     (SVDPlusPlus.py:90-103)
+ *   QREC_RATING_EUCLID  ((sign * |Q[i] - P[u]|^2 + Bi[i]) + Bu[u]) + mu, sign = +1 for EE.py:93 / SREE.py:77, which rank by the
+ *                       distance itself; |x - y|^2 is formed as (|y|^2 - 2 y.x) + |x|^2
+ *   QREC_RATING_METRIC  the EUCLID value on the rows P[u].H and Q[i].H, sign = -1 for SocialFD.py:104-112 (d_H [d][d], staged in
+ *                       LDS; d > QREC_SOCIAL_H_MAX_D returns QREC_ERR_UNSUPPORTED and writes nothing)
+ *   QREC_RATING_RSTE    Q[i].e, e = alpha P[u] + ((1 - alpha) sum_f w_f P[f]) / den[u] over the followee CSR of
+ *                       qrec_rste_sgd_ordered in its order, e = P[u] where den[u] == 0                        (RSTE.py:66-81)
+ * Arrays a form does not read may be null; an item or followee id outside its table is skipped, never dereferenced.
+ * qrec_rank_form_prepare: the item side, once per table upload, into a caller-owned buffer of qrec_rank_form_prepare_bytes
+ *   (EUCLID: |Q[i]|^2; METRIC: Q.H [n_items][ld] and its squared row norms; the other forms need 0 bytes and the call does nothing).
+ * qrec_score_topk_form: d_prep / prep_bytes = that buffer; d_scratch / scratch_bytes = qrec_score_topk_form_scratch_bytes.  Either
+ *   buffer too small, a null pointer, ld not a multiple of 16, N outside 1..100 or half a rated CSR return QREC_ERR_INVALID before
+ *   anything is written.  d_rated_indptr / d_rated_items (both or neither): the items to set to 0, any order inside a row. */
+int qrec_rank_form_prepare_bytes(int32_t form, int32_t n_items, int32_t ld, int64_t *bytes);
+int qrec_rank_form_prepare(int32_t form, const double *d_Q, const double *d_H, int32_t d, int32_t ld, int32_t n_items, void *d_prep,
+                           int64_t prep_bytes, void *stream);
+int qrec_score_topk_form_scratch_bytes(int32_t form, int32_t n_items, int32_t n_batch_users, int32_t ld, int32_t N, int64_t *bytes);
+int qrec_score_topk_form(int32_t form, double sign, const double *d_P, const double *d_Q, int32_t d, int32_t ld, int32_t n_users,
+                         int32_t n_items, const double *d_Bu, const double *d_Bi, double mu, const double *d_Y,
+                         const int64_t *d_y_indptr, const int32_t *d_y_items, const double *d_H, const int64_t *d_fe_indptr,
+                         const int32_t *d_fe_ids, const double *d_fe_w, const double *d_fe_den, double alpha, const void *d_prep,
+                         int64_t prep_bytes, const int32_t *d_user_ids, int32_t n_batch_users, const int64_t *d_rated_indptr,
+                         const int32_t *d_rated_items, int32_t N, void *d_scratch, int64_t scratch_bytes, int32_t *d_ids_out,
+                         double *d_scores_out, void *stream);
+
 /* ---- CDAE: model/ranking/CDAE.py (csrc/autoencoder.hip) -----------------------------------------------------------------
  * The denoising auto-encoder over a whole user row, evaluated only where the reference's dense batch x n_items arithmetic is
  * non-zero.  fp32; tables [rows][ld] with ld a multiple of 32 and columns [nh, ld) zero; the decoder weight is ITEM-MAJOR

@@ -74,6 +74,13 @@ class IterativeRecommender(Recommender):
             return self.U, self.V
         return self.P, self.Q
 
+    # a class whose predictForRanking is not Q.dot(P[u]) names its ranking form here (ranking.FormRanker.FORMS) and binds a
+    # FormRanker in trainModel (bind_form_ranker); without a bound ranker (a rating run, a loaded model) its host loop ranks
+    ranking_form = None
+
+    def _host_ranks(self, N):
+        return min(N, self.num_items) > 100 or (self.ranking_form is not None and getattr(self, "_form_ranker", None) is None)
+
     def rank_all_test_users(self, N):
         """The evalRanking inner loop (base/recommender.py:143-150) for all test users at
         once on the device: MFMA scoring, rated items -> 0, reference heap top-N (ties
@@ -81,8 +88,8 @@ class IterativeRecommender(Recommender):
         list (base/iterativeRecommender.py:79-80) on the host."""
         from ..ranking import DeviceRanker
         from ..util.qmath import find_k_largest
-        if min(N, self.num_items) > 100:
-            # only the per-epoch ranking_performance can ask for this (it takes max(-topN) unclamped, as the reference
+        if self._host_ranks(N):
+            # N > 100: only the per-epoch ranking_performance can ask for this (it takes max(-topN) unclamped, as the reference
             # does; the final evalRanking clamps to 10): the device ranker serves N <= 100, the reference's own loop the rest
             return super().rank_all_test_users(N)
         U, V = self.ranking_tables()
@@ -104,6 +111,10 @@ class IterativeRecommender(Recommender):
         return {u: recList[u] for u in users}   # testSet_u order, as the reference builds it
 
     def _device_ranker(self, U, V):
+        if self.ranking_form is not None:
+            ranker = self._form_ranker          # bound to the SGD object's own buffers: nothing to upload, its item side is remade
+            ranker.update_tables()
+            return ranker
         ranker = getattr(self, "_ranker", None)
         if ranker is not None and (ranker.n_users, ranker.n_items, ranker.d, ranker.dtype) == (U.shape[0], V.shape[0], U.shape[1], U.dtype):
             ranker.update_tables(U, V)             # per-epoch evaluation: keep buffers, re-upload tables
@@ -133,7 +144,7 @@ class IterativeRecommender(Recommender):
         from ..ranking import ranking_measure_strings
         from ..util.qmath import find_k_largest
         import math
-        if min(N, self.num_items) > 100:
+        if self._host_ranks(N):
             return None                      # host path (see rank_all_test_users)
         U, V = self.ranking_tables()
         U, V = np.ascontiguousarray(U), np.ascontiguousarray(V)

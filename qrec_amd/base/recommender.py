@@ -138,6 +138,18 @@ class Recommender:
                                             **buffers)
         return self._rating_eval
 
+    def bind_form_ranker(self, form, tables, **buffers):
+        """A ranking.FormRanker of ``form`` over the training set's rated items, bound to the device buffers the caller's SGD
+        object holds; kept for ``_device_ranker``.  The mirror image of ``bind_rating_evaluator``: None on a rating run, which
+        never ranks -- and None where the tables' row stride is no multiple of 16 doubles (num.factors > 128 that is no such
+        multiple); the host loop of ``rank_all_test_users`` then ranks, as it does for N > 100."""
+        self._form_ranker = None
+        if self.ranking is None or not self.ranking.isMainOn() or tables.ld % 16:
+            return None
+        from ..ranking import FormRanker
+        self._form_ranker = FormRanker(form, tables, self.data.rated_csr(), mu=self.data.globalMean, **buffers)
+        return self._form_ranker
+
     def evalRatings_host(self):
         lines = ["userId  itemId  original  prediction\n"]
         for pos, (user, item, rating) in enumerate(self.data.testData):

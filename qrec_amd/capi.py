@@ -224,6 +224,11 @@ _SIGNATURES = {
     "qrec_cfgan_read_slots": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp],
     "qrec_score_topk_sparse_row_sigmoid_bias_scratch_bytes": [_i32, _i32, _vp],
     "qrec_score_topk_sparse_row_sigmoid_bias": [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    "qrec_rank_form_prepare_bytes": [_i32, _i32, _i32, _vp],
+    "qrec_rank_form_prepare": [_i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp],
+    "qrec_score_topk_form_scratch_bytes": [_i32, _i32, _i32, _i32, _i32, _vp],
+    "qrec_score_topk_form": [_i32, _f64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp,
+                             _i64, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp],
     "qrec_apr_perturb_workspace_bytes": [_i32, _i32, _vp],
     "qrec_apr_perturb": [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _i32, _vp, _i64, _vp, _vp],
     "qrec_apr_step_workspace_bytes": [_i32, _i32, _vp],
@@ -1739,6 +1744,37 @@ def score_topk_sigmoid_bias(d_U, d_V, d_item_bias, d: int, ld: int, n_items: int
     _check(load().qrec_score_topk_sigmoid_bias(_dp(d_U), _dp(d_V), _dp(d_item_bias), d, ld, n_items, _dp(d_user_ids), n_batch_users,
                                                _dp(d_rated_indptr), _dp(d_rated_items), N, _dp(d_scratch), _dp(d_ids_out),
                                                _dp(d_scores_out), _sh(stream)))
+
+
+# ---- ranking of the rating models (csrc/rank_forms.hip): the block route with a RATING_* form as its scoring step (fp64) ----------
+def rank_form_prepare_bytes(form: int, n_items: int, ld: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_rank_form_prepare_bytes(form, n_items, ld, C.byref(out)))
+    return out.value
+
+
+def rank_form_prepare(form: int, d_Q, d_H, d: int, ld: int, n_items: int, d_prep, prep_bytes: int, stream=None):
+    """the form's item side, once per table upload: |Q[i]|^2 (EUCLID), Q.H and its row norms (METRIC), nothing for the other forms"""
+    _check(load().qrec_rank_form_prepare(form, _dp(d_Q), _dp(d_H), d, ld, n_items, _dp(d_prep), prep_bytes, _sh(stream)))
+
+
+def score_topk_form_scratch_bytes(form: int, n_items: int, n_batch_users: int, ld: int, N: int) -> int:
+    out = C.c_int64(0)
+    _check(load().qrec_score_topk_form_scratch_bytes(form, n_items, n_batch_users, ld, N, C.byref(out)))
+    return out.value
+
+
+def score_topk_form(form: int, sign: float, d_P, d_Q, d: int, ld: int, n_users: int, n_items: int, d_user_ids, n_batch_users: int,
+                    d_rated_indptr, d_rated_items, N: int, d_scratch, scratch_bytes: int, d_ids_out, d_scores_out, *, mu: float = 0.0,
+                    d_Bu=None, d_Bi=None, d_Y=None, d_y_indptr=None, d_y_items=None, d_H=None, d_fe_indptr=None, d_fe_ids=None,
+                    d_fe_w=None, d_fe_den=None, alpha: float = 0.0, d_prep=None, prep_bytes: int = 0, stream=None):
+    """top-N lists of a batch of users under one of the RATING_* ranking forms (include/qrec_hip.h); QRecError leaves the outputs
+    as they were"""
+    _check(load().qrec_score_topk_form(form, sign, _dp(d_P), _dp(d_Q), d, ld, n_users, n_items, _dp(d_Bu), _dp(d_Bi), mu, _dp(d_Y),
+                                       _dp(d_y_indptr), _dp(d_y_items), _dp(d_H), _dp(d_fe_indptr), _dp(d_fe_ids), _dp(d_fe_w),
+                                       _dp(d_fe_den), alpha, _dp(d_prep), prep_bytes, _dp(d_user_ids), n_batch_users,
+                                       _dp(d_rated_indptr), _dp(d_rated_items), N, _dp(d_scratch), scratch_bytes, _dp(d_ids_out),
+                                       _dp(d_scores_out), _sh(stream)))
 
 
 # ---- IRGAN (csrc/irgan.hip; the contract is in include/qrec_hip.h) --------------------------------------------------------------

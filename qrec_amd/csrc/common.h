@@ -84,14 +84,31 @@ int score_block_sigmoid_bias(float *S_T, const float *bias, int n_items, int b_p
 struct SparseRows { const float *W; int ld; const int64_t *indptr; const int32_t *items; const float *vals; };
 int score_block_sparse_rows(float *S_T, const SparseRows &r, int n_items, const int32_t *user_ids, int n_b, int b_pad, hipStream_t st);
 
+// S[item][b] = the ranking score of one of the QREC_RATING_* forms for user user_ids[b]: the fill pass of qrec_score_topk_form
+// (rank_forms.hip), fp64, in the place of the plain MFMA scoring of the block route.  It stages the users' operand rows, their
+// norms and biases in `ws` (form_operand_bytes), then runs the block route's own tile loop (eval_tile.h) with the form's epilogue.
+// item_op: the item-side operand [n_items][ld] (Q, or Q.H of qrec_rank_form_prepare), item_norm: its squared row norms (distance forms).
+struct FormScore {
+    int form; double sign, mu, alpha;
+    const double *P, *item_op, *item_norm; int d, ld, n_users;
+    const double *Bu, *Bi, *Y; const int64_t *y_indptr; const int32_t *y_items;
+    const double *H;
+    const int64_t *fe_indptr; const int32_t *fe_ids; const double *fe_w, *fe_den;
+    void *ws;
+};
+int64_t form_operand_bytes(int n_b, int ld);
+int score_block_form(double *S_T, const FormScore &f, int n_items, const int32_t *user_ids, int n_b, int b_pad, hipStream_t st);
+
 // ---- what crosses between the evaluation's translation units: eval_topk.hip (entry points, dispatch) calls the two routes, the
 // fused route's stage (D) calls two launches of the block route.  Kernels stay private to their files.
 // eval_block.hip: score block -> mask -> heap top-N (fp32 and fp64).  item_bias: qrec_score_topk_sigmoid_bias; sparse:
-// qrec_score_topk_sparse_row_sigmoid_bias (then U, V are unused); both fp32 only
+// qrec_score_topk_sparse_row_sigmoid_bias (then U, V are unused); both fp32 only.  form: qrec_score_topk_form (U, V unused), fp64 only
 int64_t block_path_bytes(int dtype, int n_items, int n_b);
 int run_score_topk(int dtype, const void *U, const void *V, int ld, int n_items, const int32_t *user_ids, int n_b,
                    const int64_t *rated_indptr, const int32_t *rated_items, int K, void *scratch, int32_t *ids_out, void *scores_out,
-                   hipStream_t st, const float *item_bias = nullptr, const SparseRows *sparse = nullptr);
+                   hipStream_t st, const float *item_bias = nullptr, const SparseRows *sparse = nullptr, const FormScore *form = nullptr);
+// users per wavefront (UTILE) x item tiles per wavefront of a scoring launch (eval_block.hip)
+dim3 score_grid(int n_b, int n_item_tiles, int UTILE, int min_per_wave, int *per_wave);
 // Where the fp32 score of (item, user b of the batch) goes: S[item * b_pad + (b / 64) * upair_stride + (b % 64) * u_stride].
 struct ScoreLayout { int b_pad; int64_t upair_stride, u_stride; };
 // the block route's transposed block [rows][b_pad]: what its lane-per-user scans read coalesced

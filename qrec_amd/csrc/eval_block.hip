@@ -8,7 +8,7 @@
 //       fragment in registers and streams item tiles; V (<= tens of MB) is L2/MALL resident.
 //       The block is written TRANSPOSED (item-major) so that step (3) reads coalesced.
 //       (qrec_score_topk_sigmoid_bias adds a sigmoid pass here; qrec_score_topk_sparse_row_sigmoid_bias fills the block from
-//       the rated CSR instead.)
+//       the rated CSR instead; qrec_score_topk_form fills it with a rating class's fp64 ranking scores, rank_forms.hip.)
 //   (2) mask_kernel    S_T[item][b] = 0 for the user's rated train items -- to ZERO, not -inf:
 //       the reference lets rated items compete with negative scores (recommender.py:147-149).
 //   (3) heap_topk_kernel   one lane per user walks the items in id order and keeps the
@@ -27,9 +27,6 @@
 using namespace qrec;
 
 namespace {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 // ---- (1) fp32: the tile pieces of eval_tile.h, one 64-column chunk at a time, accumulated across chunks through the output.
 // The score of (item, user b) goes to S_T[item * b_pad + (b / 64) * upair_stride + (b % 64) * u_stride]: ScoreLayout
@@ -81,75 +78,14 @@ __global__ __launch_bounds__(256) void score_kernel_f32(
     }
 }
 
-// ---- (1) fp64: 16 items x 16 users per MFMA tile, 4 slots x 16 columns per 64-chunk; the same operand fetch (ld a multiple
-// of 16 doubles, unconditional 16-byte loads, clamped rows, the next tile requested before the MFMAs).
+// ---- (1) fp64: the tile loop of eval_tile.h (score_tiles_f64: 16 items x 16 users per MFMA tile) with the identity epilogue, the
+// user operand gathered through user_ids
 __global__ __launch_bounds__(256) void score_kernel_f64(
     const double *__restrict__ U, const double *__restrict__ V, int ld, int n_items, const int32_t *__restrict__ user_ids, int n_b, int b_pad,
     int item_tiles_per_wave, double *__restrict__ S_T) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 15, h = lane >> 4;
-    const int utile = blockIdx.x;                       // 16 users
-    const int b = utile * 16 + r;
-    const int64_t uid = user_ids[b < n_b ? b : n_b - 1];
-    const int n_chunks = (ld + 63) / 64;
-    const int n_item_tiles = (n_items + 15) / 16;
-    const int t_begin = (blockIdx.y * 4 + wave) * item_tiles_per_wave;
-    int t_end = t_begin + item_tiles_per_wave;
-    if (t_end > n_item_tiles) t_end = n_item_tiles;
-    if (t_begin >= t_end) return;
-
-    for (int c = 0; c < n_chunks; c++) {
-        const int col0 = 64 * c + 16 * h;
-        const bool kv = col0 < ld;
-        const int kb = kv ? col0 : 0;
-        const double keep = kv ? 1.0 : 0.0;
-        f64x2 ub[8], va[8], vn[8];
-        {
-            const f64x2 *pu = reinterpret_cast<const f64x2 *>(U + uid * ld + kb);
-#pragma unroll
-            for (int q = 0; q < 8; q++) ub[q] = pu[q] * keep;
-        }
-        auto tile_ptr = [&](int t) {
-            const int item = t * 16 + r;
-            return reinterpret_cast<const f64x2 *>(V + (int64_t)(item < n_items ? item : n_items - 1) * ld + kb);
-        };
-        {
-            const f64x2 *pv = tile_ptr(t_begin);
-#pragma unroll
-            for (int q = 0; q < 8; q++) va[q] = pv[q];
-        }
-        for (int t = t_begin; t < t_end; t++) {
-            if (t + 1 < t_end) {
-                const f64x2 *pv = tile_ptr(t + 1);
-#pragma unroll
-                for (int q = 0; q < 8; q++) vn[q] = pv[q];
-            }
-            f64x4 acc;
-            double *out = S_T + (int64_t)(t * 16) * b_pad + utile * 16;
-            if (c == 0) {
-                acc[0] = acc[1] = acc[2] = acc[3] = 0.0;
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int row = h + 4 * q;
-                    acc[q] = (t * 16 + row < n_items) ? out[(int64_t)row * b_pad + r] : 0.0;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(va[q].x, ub[q].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(va[q].y, ub[q].y, acc, 0, 0, 0);
-            }
-            // f64 C/D: col = lane&15 (user), row = (lane>>4) + 4*reg (item)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int row = h + 4 * q;
-                if (t * 16 + row < n_items) out[(int64_t)row * b_pad + r] = acc[q];
-            }
-#pragma unroll
-            for (int q = 0; q < 8; q++) va[q] = vn[q];
-        }
-    }
+    const int b = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int64_t uid = user_ids[b < n_b ? b : n_b - 1];      // columns >= n_b are never read
+    score_tiles_f64(U, uid, V, ld, n_items, b_pad, item_tiles_per_wave, S_T, PlainScore{});
 }
 
 // ---- (2) rated train items -> score 0
@@ -485,17 +421,6 @@ BlockWs<T> block_layout(Carver &c, int n_items, int n_b) {
     return w;
 }
 
-// users per wavefront (UTILE) x item tiles per wavefront: enough waves to fill 256 CUs x 4 SIMDs a few times over, each streaming
-// >= min_per_wave item tiles
-dim3 score_grid(int n_b, int n_item_tiles, int UTILE, int min_per_wave, int *per_wave) {
-    const int n_utiles = (n_b + UTILE - 1) / UTILE;
-    const int splits = (4096 + n_utiles - 1) / n_utiles;    // item-range splits per user tile, in waves
-    *per_wave = (n_item_tiles + splits - 1) / splits;
-    if (*per_wave < min_per_wave) *per_wave = n_item_tiles < min_per_wave ? n_item_tiles : min_per_wave;
-    const int waves_per_utile = (n_item_tiles + *per_wave - 1) / *per_wave;
-    return dim3((unsigned)n_utiles, (unsigned)((waves_per_utile + 3) / 4));
-}
-
 template <typename T>
 int launch_mask(const int32_t *user_ids, int n_b, const int64_t *rated_indptr, const int32_t *rated_items, T *S, ScoreLayout lay, hipStream_t st) {
     hipLaunchKernelGGL(mask_kernel<T>, dim3((unsigned)((n_b + 3) / 4)), dim3(256), 0, st, user_ids, n_b, rated_indptr, rated_items, lay.b_pad, S,
@@ -507,7 +432,8 @@ int launch_mask(const int32_t *user_ids, int n_b, const int64_t *rated_indptr, c
 template <typename T>
 int run_block_topk(const void *U, const void *V, int ld, int n_items, const int32_t *user_ids,
                    int n_b, const int64_t *rated_indptr, const int32_t *rated_items, int K, void *scratch,
-                   int32_t *ids_out, void *scores_out, hipStream_t st, const float *item_bias, const SparseRows *sparse) {
+                   int32_t *ids_out, void *scores_out, hipStream_t st, const float *item_bias, const SparseRows *sparse,
+                   const FormScore *form) {
     const int b_pad = (n_b + 63) / 64 * 64;
     const BlockWs<T> w = carve(scratch, block_layout<T>, n_items, n_b);
     T *S_T = w.S_T;
@@ -523,6 +449,9 @@ int run_block_topk(const void *U, const void *V, int ld, int n_items, const int3
             const int rc = score_block_sigmoid_bias(S_T, item_bias, n_items, b_pad, st);
             if (rc != QREC_OK) return rc;
         }
+    } else if (form) {         // qrec_score_topk_form: the block holds one of the rating classes' ranking scores, not U V^T
+        const int rc = score_block_form(S_T, *form, n_items, user_ids, n_b, b_pad, st);
+        if (rc != QREC_OK) return rc;
     } else {
         int per_wave;
         const dim3 grid = score_grid(n_b, (n_items + 15) / 16, 16, 8, &per_wave);
@@ -587,6 +516,17 @@ int run_block_topk(const void *U, const void *V, int ld, int n_items, const int3
 
 namespace qrec {
 
+// users per wavefront (UTILE) x item tiles per wavefront: enough waves to fill 256 CUs x 4 SIMDs a few times over, each streaming
+// >= min_per_wave item tiles
+dim3 score_grid(int n_b, int n_item_tiles, int UTILE, int min_per_wave, int *per_wave) {
+    const int n_utiles = (n_b + UTILE - 1) / UTILE;
+    const int splits = (4096 + n_utiles - 1) / n_utiles;    // item-range splits per user tile, in waves
+    *per_wave = (n_item_tiles + splits - 1) / splits;
+    if (*per_wave < min_per_wave) *per_wave = n_item_tiles < min_per_wave ? n_item_tiles : min_per_wave;
+    const int waves_per_utile = (n_item_tiles + *per_wave - 1) / *per_wave;
+    return dim3((unsigned)n_utiles, (unsigned)((waves_per_utile + 3) / 4));
+}
+
 int64_t block_path_bytes(int dtype, int n_items, int n_b) {
     return dtype == QREC_F64 ? layout_bytes(block_layout<double>, n_items, n_b) : layout_bytes(block_layout<float>, n_items, n_b);
 }
@@ -608,12 +548,12 @@ int launch_mask_block(const int32_t *user_ids, int n_b, const int64_t *rated_ind
 
 int run_score_topk(int dtype, const void *U, const void *V, int ld, int n_items, const int32_t *user_ids, int n_b,
                    const int64_t *rated_indptr, const int32_t *rated_items, int K, void *scratch, int32_t *ids_out, void *scores_out,
-                   hipStream_t st, const float *item_bias, const SparseRows *sparse) {
+                   hipStream_t st, const float *item_bias, const SparseRows *sparse, const FormScore *form) {
     return dtype == QREC_F64
                ? run_block_topk<double>(U, V, ld, n_items, user_ids, n_b, rated_indptr, rated_items, K, scratch, ids_out, scores_out, st,
-                                        nullptr, nullptr)
+                                        nullptr, nullptr, form)
                : run_block_topk<float>(U, V, ld, n_items, user_ids, n_b, rated_indptr, rated_items, K, scratch, ids_out, scores_out, st,
-                                       item_bias, sparse);
+                                       item_bias, sparse, nullptr);
 }
 
 }  // namespace qrec

@@ -3,12 +3,15 @@
 // re-scoring of select_topk_kernel in eval_fused.hip) run v_mfma_f32_32x32x2_f32 over chunks of 64 columns; the bf16 kernels
 // (sample_max_bf16_kernel, score_filter_bf16_kernel) run v_mfma_f32_32x32x16_bf16 over slices of 16.  A kernel is these pieces
 // plus its own epilogue.  Lane l of a wavefront is (r, h) = (l & 31, l >> 5): operand row r, k-slot h; accumulator register q of
-// lane (r, h) is user column r, item row cd_row(q, h) of the tile (mfma_rows.h).
+// lane (r, h) is user column r, item row cd_row(q, h) of the tile (mfma_rows.h).  The fp64 loop (16 x 16 tiles, v_mfma_f64_16x16x4_f64)
+// is one function with an epilogue functor, score_tiles_f64: score_kernel_f64 of eval_block.hip and score_form_kernel of rank_forms.hip.
 //
 // Operand fetch: the tables are zero-padded to the row stride ld (a multiple of 32 floats), so a lane reads ITS row's slot with
 // unconditional 16-byte loads; rows past the end are clamped (their results are not stored).  (First version: one guarded dword
 // load per element, 81 loads and 99 branches per 32 MFMAs.)
 #pragma once
+#include <type_traits>
+
 #include "mfma_rows.h"
 
 namespace qrec {
@@ -78,6 +81,95 @@ __device__ __forceinline__ void mfma_f32(const f32x4 (&v)[NC][8], Chains... chai
         for (int q = 0; q < 8; q++)
 #pragma unroll
             for (int j = 0; j < 4; j++) ((chains.acc = __builtin_amdgcn_mfma_f32_32x32x2f32(v[c][q][j], chains.u[c][q][j], chains.acc, 0, 0, 0)), ...);
+}
+
+// ---- fp64: 16 items x 16 users per MFMA tile (v_mfma_f64_16x16x4_f64), 4 slots x 16 columns per 64-chunk; the same operand fetch
+// (ld a multiple of 16 doubles, unconditional 16-byte loads, clamped rows, the next tile requested before the MFMAs).  Lane l is
+// (r, h) = (l & 15, l >> 4): user column r of user tile `utile`, whose operand row is `urow` (U + urow * ld); accumulator register q
+// is item row h + 4 q.  Chunks accumulate through the output block; on the LAST chunk epi(dot, item, b) turns the finished inner
+// product of (item, user b = utile * 16 + r of the batch) into the stored score.  score_kernel_f64 (eval_block.hip) passes the
+// identity and U[user_ids[b]]; the form scoring of rank_forms.hip passes its bias / distance epilogue and row b of a staged operand.
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+struct PlainScore {
+    __device__ __forceinline__ double operator()(double dot, int, int) const { return dot; }
+};
+
+template <typename Epi>
+__device__ __forceinline__ void score_tiles_f64(const double *__restrict__ U, int64_t urow, const double *__restrict__ V, int ld, int n_items,
+                                                int b_pad, int item_tiles_per_wave, double *__restrict__ S_T, const Epi epi) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 15, h = lane >> 4;
+    const int utile = blockIdx.x;                       // 16 users
+    const int n_chunks = (ld + 63) / 64;
+    const int n_item_tiles = (n_items + 15) / 16;
+    const int t_begin = (blockIdx.y * 4 + wave) * item_tiles_per_wave;
+    int t_end = t_begin + item_tiles_per_wave;
+    if (t_end > n_item_tiles) t_end = n_item_tiles;
+    if (t_begin >= t_end) return;
+
+    for (int c = 0; c < n_chunks; c++) {
+        const int col0 = 64 * c + 16 * h;
+        const bool kv = col0 < ld;
+        const int kb = kv ? col0 : 0;
+        const double keep = kv ? 1.0 : 0.0;
+        f64x2 ub[8], va[8], vn[8];
+        {
+            const f64x2 *pu = reinterpret_cast<const f64x2 *>(U + urow * ld + kb);
+#pragma unroll
+            for (int q = 0; q < 8; q++) ub[q] = pu[q] * keep;
+        }
+        auto tile_ptr = [&](int t) {
+            const int item = t * 16 + r;
+            return reinterpret_cast<const f64x2 *>(V + (int64_t)(item < n_items ? item : n_items - 1) * ld + kb);
+        };
+        {
+            const f64x2 *pv = tile_ptr(t_begin);
+#pragma unroll
+            for (int q = 0; q < 8; q++) va[q] = pv[q];
+        }
+        for (int t = t_begin; t < t_end; t++) {
+            if (t + 1 < t_end) {
+                const f64x2 *pv = tile_ptr(t + 1);
+#pragma unroll
+                for (int q = 0; q < 8; q++) vn[q] = pv[q];
+            }
+            f64x4 acc;
+            double *out = S_T + (int64_t)(t * 16) * b_pad + utile * 16;
+            if (c == 0) {
+                acc[0] = acc[1] = acc[2] = acc[3] = 0.0;
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int row = h + 4 * q;
+                    acc[q] = (t * 16 + row < n_items) ? out[(int64_t)row * b_pad + r] : 0.0;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(va[q].x, ub[q].x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(va[q].y, ub[q].y, acc, 0, 0, 0);
+            }
+            // f64 C/D: col = lane&15 (user), row = (lane>>4) + 4*reg (item)
+            if constexpr (!std::is_same<Epi, PlainScore>::value) {
+                if (c == n_chunks - 1) {
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const int item = t * 16 + h + 4 * q;
+                        if (item < n_items) acc[q] = epi(acc[q], item, utile * 16 + r);
+                    }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int row = h + 4 * q;
+                if (t * 16 + row < n_items) out[(int64_t)row * b_pad + r] = acc[q];
+            }
+#pragma unroll
+            for (int q = 0; q < 8; q++) va[q] = vn[q];
+        }
+    }
 }
 
 // ---- bf16: NM = ld / 16 MFMAs per tile; lane (r, h) holds columns 16 m + 8 h .. + 8 of its row for every slice m

@@ -11,6 +11,8 @@ from ...engine import DeviceTables, MfSgd
 
 
 class EE(IterativeRecommender):
+    ranking_form = "EUCLID"      # predictForRanking on the device: ranking.FormRanker
+
     def __init__(self, conf, trainingSet=None, testSet=None, fold="[1]"):
         super().__init__(conf, trainingSet, testSet, fold)
 
@@ -26,6 +28,7 @@ class EE(IterativeRecommender):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = MfSgd(tables, self.data.elemCount(), capi.MF_EE, self.Bu, self.Bi)
         self.bind_rating_evaluator("EUCLID", tables, Bu=sgd.d_Bu, Bi=sgd.d_Bi)
+        self.bind_form_ranker("EUCLID", tables, Bu=sgd.d_Bu, Bi=sgd.d_Bi, sign=1.0)      # predictForRanking ADDS the distance
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()
@@ -49,10 +52,3 @@ class EE(IterativeRecommender):
             u = self.data.user[u]
             return ((self.Q - self.P[u]) * (self.Q - self.P[u])).sum(axis=1) + self.Bi + self.Bu[u] + self.data.globalMean
         return [self.data.globalMean] * self.num_items
-
-    def rank_all_test_users(self, N):
-        from ...base.recommender import Recommender
-        return Recommender.rank_all_test_users(self, N)      # scores are not an inner product: the generic host loop
-
-    def rank_measure_all_test_users(self, top, N):
-        return None

@@ -12,6 +12,8 @@ from ...util import config
 
 
 class RSTE(SocialRecommender):
+    ranking_form = "RSTE"        # predictForRanking on the device: ranking.FormRanker
+
     def __init__(self, conf, trainingSet=None, testSet=None, relation=list(), fold="[1]"):
         super().__init__(conf, trainingSet, testSet, relation, fold)
 
@@ -32,6 +34,7 @@ class RSTE(SocialRecommender):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = SocialSgd(tables, self.data.elemCount(), "RSTE", followee_csr_by_user(self))
         self.bind_rating_evaluator("RSTE", tables, followees=(sgd.d_fe_ptr, sgd.d_fe_ids, sgd.d_fe_w, sgd.d_den), alpha=self.alpha)
+        self.bind_form_ranker("RSTE", tables, followees=(sgd.d_fe_ptr, sgd.d_fe_ids, sgd.d_fe_w, sgd.d_den), alpha=self.alpha)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()
@@ -70,10 +73,3 @@ class RSTE(SocialRecommender):
                 return self.alpha * self.Q.dot(self.P[u]) + (1 - self.alpha) * fPred / denom
             return self.Q.dot(self.P[u])
         return [self.data.globalMean] * len(self.data.item)
-
-    def rank_all_test_users(self, N):
-        from ...base.recommender import Recommender
-        return Recommender.rank_all_test_users(self, N)      # scores are not one inner product: the generic host loop
-
-    def rank_measure_all_test_users(self, top, N):
-        return None

@@ -13,6 +13,8 @@ from ...util import config
 
 
 class SREE(SocialRecommender):
+    ranking_form = "EUCLID"      # predictForRanking on the device: ranking.FormRanker
+
     def __init__(self, conf, trainingSet=None, testSet=None, relation=list(), fold="[1]"):
         super().__init__(conf, trainingSet, testSet, relation, fold)
 
@@ -32,6 +34,7 @@ class SREE(SocialRecommender):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = SocialSgd(tables, self.data.elemCount(), "SREE", user_steps(self), Bu=self.Bu, Bi=self.Bi)
         self.bind_rating_evaluator("EUCLID", tables, Bu=sgd.mf.d_Bu, Bi=sgd.mf.d_Bi)
+        self.bind_form_ranker("EUCLID", tables, Bu=sgd.mf.d_Bu, Bi=sgd.mf.d_Bi, sign=1.0)      # predictForRanking ADDS the distance
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()
@@ -56,10 +59,3 @@ class SREE(SocialRecommender):
             u = self.data.user[u]
             return ((self.Q - self.P[u]) * (self.Q - self.P[u])).sum(axis=1) + self.Bi + self.Bu[u] + self.data.globalMean
         return [self.data.globalMean] * len(self.data.item)
-
-    def rank_all_test_users(self, N):
-        from ...base.recommender import Recommender
-        return Recommender.rank_all_test_users(self, N)      # scores are not one inner product: the generic host loop
-
-    def rank_measure_all_test_users(self, top, N):
-        return None

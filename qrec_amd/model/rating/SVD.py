@@ -11,6 +11,8 @@ from ...engine import DeviceTables, MfSgd
 
 
 class SVD(IterativeRecommender):
+    ranking_form = "BIASED"      # predictForRanking on the device: ranking.FormRanker
+
     def __init__(self, conf, trainingSet=None, testSet=None, fold="[1]"):
         super().__init__(conf, trainingSet, testSet, fold)
 
@@ -26,6 +28,7 @@ class SVD(IterativeRecommender):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = MfSgd(tables, self.data.elemCount(), capi.MF_SVD, self.Bu, self.Bi)
         self.bind_rating_evaluator("BIASED", tables, Bu=sgd.d_Bu, Bi=sgd.d_Bi)
+        self.bind_form_ranker("BIASED", tables, Bu=sgd.d_Bu, Bi=sgd.d_Bi)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()
@@ -48,13 +51,3 @@ class SVD(IterativeRecommender):
             u = self.data.getUserId(u)
             return self.Q.dot(self.P[u]) + self.data.globalMean + self.Bi + self.Bu[u]
         return [self.data.globalMean] * self.num_items
-
-    def ranking_tables(self):
-        raise NotImplementedError   # scores carry bias terms: the generic host loop ranks this model
-
-    def rank_all_test_users(self, N):
-        from ...base.recommender import Recommender
-        return Recommender.rank_all_test_users(self, N)
-
-    def rank_measure_all_test_users(self, top, N):
-        return None

@@ -11,6 +11,8 @@ from ...util import config
 
 
 class SVDPlusPlus(IterativeRecommender):
+    ranking_form = "SVDPP"       # predictForRanking on the device: ranking.FormRanker
+
     def __init__(self, conf, trainingSet=None, testSet=None, fold="[1]"):
         super().__init__(conf, trainingSet, testSet, fold)
 
@@ -38,6 +40,7 @@ class SVDPlusPlus(IterativeRecommender):
         sgd = SvdppSgd(tables, self.Y, self.Bu, self.Bi, self.data.rated_csr(), self.data.elemCount())
         self.bind_rating_evaluator("SVDPP", tables, Bu=sgd.d_Bu, Bi=sgd.d_Bi, Y=sgd.d_Y,
                                    rated=(sgd.d_indptr, sgd.d_items, self.data.rated_csr().indptr))
+        self.bind_form_ranker("SVDPP", tables, Bu=sgd.d_Bu, Bi=sgd.d_Bi, Y=sgd.d_Y, y_rated=(sgd.d_indptr, sgd.d_items))
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()
@@ -82,10 +85,3 @@ class SVDPlusPlus(IterativeRecommender):
         else:
             pred = [self.data.globalMean] * len(self.data.item)
         return pred
-
-    def rank_all_test_users(self, N):
-        from ...base.recommender import Recommender
-        return Recommender.rank_all_test_users(self, N)
-
-    def rank_measure_all_test_users(self, top, N):
-        return None

@@ -3,7 +3,8 @@
 (r <= 0.5, two branches on the distance) and medium ratings differently, the social pass pulls every user towards its
 followees under the same metric.  x = P[u], y = Q[i] are views in the reference and stay so here.  Both passes are
 order-exact device kernels (fp64); the d x d matrix H stays in LDS for a whole pass (social.hip), which bounds
-num.factors by 128.  Ranking scores are quadratic forms, not one inner product: the generic host loop ranks."""
+num.factors by 128.  A ranking score is a quadratic form in x - y: a squared distance of the rows projected by H, which is how the
+device ranks it (ranking.FormRanker, form METRIC)."""
 from __future__ import annotations
 
 import numpy as np
@@ -16,6 +17,8 @@ from ...util import config
 
 
 class SocialFD(SocialRecommender):
+    ranking_form = "METRIC"      # predictForRanking on the device: ranking.FormRanker
+
     def __init__(self, conf, trainingSet=None, testSet=None, relation=list(), fold="[1]"):
         super().__init__(conf, trainingSet, testSet, relation, fold)
 
@@ -43,6 +46,7 @@ class SocialFD(SocialRecommender):
         tables = DeviceTables(self.P, self.Q, np.float64)
         sgd = SocialHSgd(tables, self.data.elemCount(), "SocialFD", socialfd_steps(self), self.H, Bu=self.Bu, Bi=self.Bi)
         self.bind_rating_evaluator("METRIC", tables, Bu=sgd.d_Bu, Bi=sgd.d_Bi, H=sgd.d_H)
+        self.bind_form_ranker("METRIC", tables, Bu=sgd.d_Bu, Bi=sgd.d_Bi, H=sgd.d_H, sign=-1.0)
         epoch = 0
         while epoch < self.maxEpoch:
             u, i, r = self.data.training_arrays()
@@ -70,10 +74,3 @@ class SocialFD(SocialRecommender):
             A = self.H.dot(self.H.T)
             return self.Bi + self.Bu[u] + self.data.globalMean - (diff.dot(A) * diff).sum(axis=1)
         return np.array([self.data.globalMean] * len(self.data.item))
-
-    def rank_all_test_users(self, N):
-        from ...base.recommender import Recommender
-        return Recommender.rank_all_test_users(self, N)      # scores are not one inner product: the generic host loop
-
-    def rank_measure_all_test_users(self, top, N):
-        return None

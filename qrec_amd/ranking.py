@@ -174,6 +174,79 @@ class SparseRowSigmoidRanker(DeviceRanker):
                                                 self.d_vals, N, scratch, d_ids, d_sc)
 
 
+class FormRanker(DeviceRanker):
+    """The rating models whose ranking score is not one plain inner product -- SVD, SVDPlusPlus, EE, SREE, RSTE, SocialFD
+    (their predictForRanking; include/qrec_hip.h, qrec_score_topk_form): the block route with the class's fp64 form as its scoring
+    step, rated train items then set to 0 and the reference's heap top-N as everywhere else.
+
+    ``form`` names the score (capi.RATING_*, or its name as engine.RatingEvaluator.FORMS spells it).  The ranker BINDS device
+    buffers and copies none: ``tables`` (an engine.DeviceTables, fp64) and by keyword ``Bu`` / ``Bi`` (MfSgd.d_Bu / d_Bi), ``Y``
+    with ``y_rated`` = (d_indptr, d_items) in userRated order (SvdppSgd), ``H`` (SocialHSgd.d_H), ``followees`` = (d_ptr, d_ids,
+    d_w, d_den) with ``alpha`` (SocialSgd, RSTE); ``mu`` = the global mean, ``sign`` = +1 (EE, SREE rank by the distance itself)
+    or -1 (SocialFD).  Its own buffer is the form's prepared item side (|Q[i]|^2, or Q.H and its norms), remade by
+    ``update_tables`` -- call it whenever the bound tables have changed.  ``topk`` / ``set_test`` are the base class's."""
+    FORMS = {"DOT": capi.RATING_DOT, "BIASED": capi.RATING_BIASED, "SVDPP": capi.RATING_SVDPP, "EUCLID": capi.RATING_EUCLID,
+             "METRIC": capi.RATING_METRIC, "RSTE": capi.RATING_RSTE}
+
+    def __init__(self, form, tables, rated: CSR | None = None, *, mu: float = 0.0, sign: float = 1.0, Bu=None, Bi=None, Y=None,
+                 y_rated=None, H=None, followees=None, alpha: float = 0.0):
+        self.form = self.FORMS[form] if isinstance(form, str) else int(form)
+        if self.form not in self.FORMS.values():
+            raise ValueError(f"unknown ranking form {form!r}")
+        if tables.dtype != np.float64:
+            raise ValueError("the form ranker runs on fp64 tables")
+        if self.form == capi.RATING_METRIC and tables.d > capi.SOCIAL_H_MAX_D:
+            raise ValueError(f"the METRIC form supports num.factors <= {capi.SOCIAL_H_MAX_D} (the d x d matrix H stays in LDS), got {tables.d}")
+        if tables.ld % 16:
+            raise ValueError(f"the form ranker needs a row stride that is a multiple of 16 doubles, got {tables.ld}")
+        needs = {capi.RATING_BIASED: (Bu, Bi), capi.RATING_SVDPP: (Bu, Bi, Y, y_rated), capi.RATING_EUCLID: (Bu, Bi),
+                 capi.RATING_METRIC: (Bu, Bi, H), capi.RATING_RSTE: (followees,)}.get(self.form, ())
+        if any(x is None for x in needs):
+            raise ValueError("the form's device buffers are missing (Bu/Bi, Y and y_rated, H or followees)")
+        if self.form in (capi.RATING_EUCLID, capi.RATING_METRIC) and sign not in (1.0, -1.0):
+            raise ValueError("sign must be +1 or -1")
+        self._init_state(np.float64, tables.d, tables.ld, tables.n_users, tables.n_items, rated)
+        self.t = tables
+        self.mu, self.sign, self.alpha = float(mu), float(sign), float(alpha)
+        self.d_Bu, self.d_Bi, self.d_Y, self.d_H = Bu, Bi, Y, H
+        self.d_y = y_rated if y_rated is not None else (None, None)
+        self.d_fe = followees if followees is not None else (None, None, None, None)
+        self.prep_bytes = capi.rank_form_prepare_bytes(self.form, self.n_items, self.ld)
+        self.d_prep = DeviceBuffer(self.prep_bytes, np.uint8) if self.prep_bytes else None
+        self.update_tables()
+
+    def update_tables(self, *_):
+        """the bound tables have new values (an epoch ran): remake the prepared item side from them"""
+        capi.rank_form_prepare(self.form, self.t.Q, self.d_H, self.d, self.ld, self.n_items, self.d_prep, self.prep_bytes)
+
+    def _scratch_bytes(self, n_batch_users: int, N: int) -> int:
+        return capi.score_topk_form_scratch_bytes(self.form, self.n_items, n_batch_users, self.ld, N)
+
+    def _score_topk(self, d_users, n: int, N: int, scratch, d_ids, d_sc):
+        capi.score_topk_form(self.form, self.sign, self.t.P, self.t.Q, self.d, self.ld, self.n_users, self.n_items, d_users, n,
+                             self.rated[0] if self.rated else None, self.rated[1] if self.rated else None, N, scratch, scratch.nbytes,
+                             d_ids, d_sc, mu=self.mu, d_Bu=self.d_Bu, d_Bi=self.d_Bi, d_Y=self.d_Y, d_y_indptr=self.d_y[0],
+                             d_y_items=self.d_y[1], d_H=self.d_H, d_fe_indptr=self.d_fe[0], d_fe_ids=self.d_fe[1], d_fe_w=self.d_fe[2],
+                             d_fe_den=self.d_fe[3], alpha=self.alpha, d_prep=self.d_prep, prep_bytes=self.prep_bytes)
+
+    @classmethod
+    def from_host(cls, form, P, Q, rated: CSR | None = None, *, mu: float = 0.0, sign: float = 1.0, Bu=None, Bi=None, Y=None,
+                  y_rated: CSR | None = None, H=None, followees=None, alpha: float = 0.0):
+        """the same ranker over host arrays, uploaded here (tests and tools); ``y_rated``: a CSR of every user's train items in
+        userRated order, ``followees``: (ptr, ids, w, den) as social.followee_csr_by_user returns them"""
+        from .engine import DeviceTables
+        t = DeviceTables(np.asarray(P, dtype=np.float64), np.asarray(Q, dtype=np.float64), np.float64)
+        up = lambda a, dt: None if a is None else DeviceBuffer.from_numpy(np.ascontiguousarray(a, dtype=dt) if np.size(a) else np.zeros(1, dt))
+        kw = dict(mu=mu, sign=sign, alpha=alpha, Bu=up(Bu, np.float64), Bi=up(Bi, np.float64), H=up(H, np.float64))
+        if Y is not None:
+            kw["Y"] = DeviceBuffer.from_numpy(t._pad(np.asarray(Y, dtype=np.float64)))
+            kw["y_rated"] = (up(y_rated.indptr, np.int64), up(y_rated.indices, np.int32))
+        if followees is not None:
+            ptr, ids, w, den = followees
+            kw["followees"] = (up(ptr, np.int64), up(ids, np.int32), up(w, np.float64), up(den, np.float64))
+        return cls(form, t, rated, **kw)
+
+
 def ranking_measure_strings(test_lens, per_n: dict, Ns) -> list:
     """The strings of Measure.rankingMeasure (util/measure.py:24-49) from per-user hit counts and DCG sums:
     ``per_n[n] = (hits, dcg)`` sequences in testSet_u order, ``test_lens[k] = len(testSet_u[user_k])``.  Same
